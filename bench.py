@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- VAE train images/sec on MI355X (BASELINE.json metric), one process per GPU.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Workload at N=1 = BASELINE.json configs[1]: beta-VAE (beta=4) on dSprites-shaped synthetic
@@ -10,11 +10,18 @@ per-GPU batch fixed, gradients summed by ONE RCCL all-reduce of the flat fp32 bu
 A "step" = forward + backward + slab reduction + (all-reduce) + Adam on one batch already
 resident in HBM.  Prints ONE JSON line (rank 0).
 
-Extra objects in the JSON line:
+A plain run sets up, conditions and warms up, times K steps and prints the headline line
+(images/sec, ms_per_step).  Every run executes the same number of steps on the same seeded
+inputs, so `--dump-outputs DIR` (the last timed step's loss terms and the trained weights as
+DIR/<name>.npy) compares two builds output for output.
+
+`--full` adds the measurements that take runs of their own:
   roofline     -- the dominant kernel launch, timed live with HIP events on the launch
                   stream; algorithmic FLOPs / bytes per launch are stated in DESIGN.md.
+  hbm_kernels  -- the HBM-bound kernels stand-alone, cold and cache-hot.
   cpu_baseline -- the same training step as a torch-CPU fp32 port (oracle/torch_ref.py,
                   all host cores), rank 0 at N=1 only, on a bounded number of steps.
+  north_star_3ch, fit, exact_fp32 (default workload), mel_kernel (speech), rccl.allreduce_us.
 """
 import argparse
 import json
@@ -573,6 +580,21 @@ def time_allreduce(eng, reps=20):
   return e0.elapsed_time(e1) / reps * 1e3
 
 
+DUMP_MAX_ELEMS = 1 << 22  # per array (16 MiB of float32): the three large ones a run can dump stay under 64 MB
+
+
+def dump_outputs(out_dir, arrays):
+  """arrays: {name: device tensor} -> out_dir/<name>.npy in float32.  An array longer than
+  DUMP_MAX_ELEMS is written as a fixed, seeded sample of its flattened elements (sorted
+  indices), the same sample in every run."""
+  os.makedirs(out_dir, exist_ok=True)
+  for name, t in arrays.items():
+    a = t.detach().float().cpu().numpy()
+    if a.size > DUMP_MAX_ELEMS:
+      a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, DUMP_MAX_ELEMS, replace=False))]
+    np.save(os.path.join(out_dir, name + '.npy'), a.astype(np.float32))
+
+
 _JSON_OUT = None
 
 
@@ -595,6 +617,11 @@ def main():
   ap.add_argument('--steps', type=int, default=100)
   ap.add_argument('--warmup', type=int, default=20)
   ap.add_argument('--workload', default='dsprites_betavae_b256', choices=sorted(WORKLOADS))
+  ap.add_argument('--full', action='store_true',
+                  help='after the headline steps, also measure what takes runs of its own: per-kernel roofline, HBM '
+                  'kernels, CPU baseline, the 64x64x3 line, fit(), exact fp32, front-end launch, all-reduce alone')
+  ap.add_argument('--dump-outputs', metavar='DIR',
+                  help="write the last timed step's outputs (loss terms, trained weights) as DIR/<name>.npy")
   ap.add_argument('--no-cpu-baseline', action='store_true')
   ap.add_argument('--cpu-steps', type=int, default=25)
   ap.add_argument('--no-graph', action='store_true')
@@ -633,6 +660,10 @@ def main():
                   help='initialise the RCCL process group even at world size 1, so that the '
                   'data-parallel step (graph A, RCCL all-reduce, graph B) runs on a 1-GPU box')
   args = ap.parse_args()
+  if args.steps < 1 or args.warmup < 0:
+    ap.error('--steps must be >= 1 and --warmup >= 0')
+  if args.profile_ops and not args.full:
+    ap.error('--profile-ops prints the per-kernel table that --full measures: add --full')
 
   import ast
   eopts = {}
@@ -770,7 +801,9 @@ def main():
   # Steady-state conditioning before the W warm-up steps: on a freshly started process the first
   # ~100 ms of replays can run 20-30 % slow (clock / power ramp from idle; measured as one slow
   # first block of 100 steps in about 1 process out of 8, steady afterwards), so the GPU is kept
-  # busy for ~0.6 s first.  Untimed, like the graph capture itself.
+  # busy for ~0.6 s first.  Untimed, like the graph capture itself.  A fixed number of steps (1400: ~0.63 s
+  # of the default workload), not a wall-clock budget: every run trains through the same steps, so the
+  # outputs of the last timed step are the same from run to run and comparable between two builds.
   step()
   torch.cuda.synchronize()
   if use_dist:
@@ -779,13 +812,10 @@ def main():
       step()
     torch.cuda.synchronize()
   else:
-    t_pw = time.perf_counter()
-    blocks = 0
-    while time.perf_counter() - t_pw < 0.6:
+    for blocks in range(1, 71):
       for _ in range(20):
         step()
       torch.cuda.synchronize()
-      blocks += 1
       if os.environ.get('ODIN_BENCH_TRACE_FLAG') and eng.flag.item() != 0:
         print(f'bench.py: non-finite gradients first seen in conditioning block {blocks} (20 steps each)',
               file=sys.stderr)
@@ -822,7 +852,8 @@ def main():
     dist.all_reduce(lo, op=dist.ReduceOp.MIN)
     dist.all_reduce(hi, op=dist.ReduceOp.MAX)
     rccl['replicas_in_sync'] = bool(lo.item() == hi.item())
-    rccl['allreduce_us'] = round(time_allreduce(eng), 2)
+    if args.full:
+      rccl['allreduce_us'] = round(time_allreduce(eng), 2)
     rccl['transport'] = ('RCCL through the C ABI (odin_allreduce_flat, own communicator)'
                          if eng._comm().native else 'torch.distributed ' + dist.get_backend())
     rccl['dp_buckets'] = eng.dp_buckets
@@ -836,202 +867,20 @@ def main():
   if eng.flag.item() != 0:
     describe_nonfinite(eng)
   assert eng.flag.item() == 0, 'non-finite gradients were skipped during the timed region'
+  if args.dump_outputs and rank == 0:
+    # what a caller of the step receives: its loss terms [loss, llk, beta*kl, tc] and the trained weights (before
+    # any --full measurement reuses the engine's buffers)
+    arrays = dict(loss_terms=out, params=eng.params)
+    if fv is not None:
+      arrays['disc_params'] = fv._discriminator(B // 2).params
+    if kind == 'speech':
+      arrays['mel_frames'] = xb   # the front-end's output inside the step
+    dump_outputs(args.dump_outputs, arrays)
 
   if rank != 0:
     dist.destroy_process_group()
     return
 
-  # ---- roofline of the dominant kernel (per-launch, HIP events on the launch stream) ----
-  # Kernels whose path ends in "(bf16x3)" carry fp32 operands through the bf16 matrix pipe as three
-  # exact planes (6 bf16 MFMAs per 16 k-values): they are priced against the bf16 peak with the bf16
-  # FLOPs they execute (6 x the fp32 FLOPs of the convolution) in `roofline_split`;
-  # `roofline` is the dominant kernel among those that compute in fp32 MFMAs.
-  ops = profile_ops(eng)
-  is_split = lambda o: o.get('path', '').endswith('(f16x2)')
-  fp32_ops = [o for o in ops if not is_split(o)] or ops
-  dom = max(fp32_ops, key=lambda o: o['us'])
-  roofline = dict(bound='mfma', kernel=f"{dom['layer']}:{dom['op']}", path=dom.get('path'),
-                  achieved=round(dom['tflops'], 3), peak=PEAK_MFMA_F32_TFLOPS, unit='TFLOP/s',
-                  frac=round(dom['tflops'] / PEAK_MFMA_F32_TFLOPS, 4), traffic=None,
-                  us_per_launch=round(dom['us'], 2), gflop_per_launch=round(dom['gflop'], 4),
-                  note='fp32 FLOPs / dense fp32 MFMA peak (v_mfma_f32_16x16x4_f32 / 32x32x2_f32)')
-  pmc = {}
-  try:
-    import json as _json
-    import glob as _glob
-    # the newest round's PMC table (tools/pmc_traffic.py <tag> after tools/pmc.sh <tag>)
-    _cand = sorted(_glob.glob(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'profiles',
-                                           'r*_pmc_traffic.json')))
-    pmc_file = _cand[-1]
-    pmc = _json.load(open(pmc_file))
-  except (OSError, ValueError, IndexError):
-    pmc_file = None
-
-  def attach_traffic(obj):
-    # HBM traffic from the committed PMC passes (FETCH_SIZE / WRITE_SIZE cannot be collected inside
-    # this process); null when no measurement for this kernel on this workload is on file
-    ent = pmc.get(obj['kernel'])
-    if ent is not None and args.workload == 'dsprites_betavae_b256':
-      obj['traffic'] = ent['traffic_bytes']
-      obj['traffic_unit'] = 'bytes'
-      obj['algorithmic_bytes'] = ent.get('algorithmic_bytes')
-      obj['traffic_source'] = 'profiles/' + os.path.basename(pmc_file)
-      obj['traffic_measured_in_this_run'] = False  # (PMC counters cannot be collected inside this process)
-      if ent.get('us_in_graph'):
-        # what the STEP pays for this launch: its average duration inside the captured graph under rocprofv3
-        # (profiles/<round>_kernel_stats.csv), a few us longer than the stand-alone HIP-event time of this run
-        obj['us_in_graph'] = ent['us_in_graph']
-        obj['us_in_graph_source'] = ent.get('us_in_graph_source')
-        if ent.get('algorithmic_bytes'):
-          obj['frac_in_graph'] = round(ent['algorithmic_bytes'] / (ent['us_in_graph'] * 1e-6) * 1e-9 / PEAK_HBM_GBS, 4)
-
-  attach_traffic(roofline)
-  roofline_split = None
-  split_ops = [o for o in ops if is_split(o)]
-  if split_ops:
-    # A plane kernel executes 3 f16 MFMAs per 16 k-values (fp32 operands as two f16 planes): its matrix-pipe floor
-    # is executed FLOPs / the dense f16 peak, its memory floor algorithmic bytes / 8 TB/s.  Since the two-plane form
-    # the MEMORY floor is the higher one for the big layers (arithmetic intensity ~146 executed FLOP per byte against
-    # a machine balance of 314): the kernel is priced against the roof that binds it, the other leg is kept beside.
-    so = max(split_ops, key=lambda o: o['us'])
-    f16_gflop = 3.0 * so.get('mfma_gflop', so['gflop'])
-    mfma_leg = dict(achieved=round(f16_gflop / so['us'] * 1e3, 3), peak=PEAK_MFMA_BF16_TFLOPS,
-                    unit='TFLOP/s (f16 FLOPs executed)', frac=round(f16_gflop / so['us'] * 1e3 / PEAK_MFMA_BF16_TFLOPS, 4),
-                    gflop_per_launch=round(f16_gflop, 4),
-                    fp32_equivalent_tflops=round(so['tflops'], 3),
-                    fp32_equivalent_frac_of_fp32_mfma_peak=round(so['tflops'] / PEAK_MFMA_F32_TFLOPS, 4))
-    roofline_split = dict(bound='mfma', kernel=f"{so['layer']}:{so['op']}", path=so.get('path'), traffic=None,
-                          us_per_launch=round(so['us'], 2), **mfma_leg,
-                          note='fp32 operands as 2 f16 planes: 3 v_mfma_f32_32x32x16_f16 per 16 '
-                               'k-values, priced against the dense f16 MFMA peak')
-    attach_traffic(roofline_split)
-    alg = roofline_split.get('algorithmic_bytes')
-    if alg:
-      t_hbm, t_mfma = alg / (PEAK_HBM_GBS * 1e9), f16_gflop * 1e9 / (PEAK_MFMA_BF16_TFLOPS * 1e12)
-      hbm_leg = dict(achieved=round(alg / (so['us'] * 1e-6) * 1e-9, 1), peak=PEAK_HBM_GBS, unit='GB/s',
-                     frac=round(alg / (so['us'] * 1e-6) * 1e-9 / PEAK_HBM_GBS, 4))
-      roofline_split['floors_us'] = dict(hbm=round(t_hbm * 1e6, 2), mfma=round(t_mfma * 1e6, 2))
-      if t_hbm >= t_mfma:
-        roofline_split.update(bound='hbm', mfma_leg=mfma_leg, **hbm_leg)
-        roofline_split['note'] = ('memory-bound by the roofline model: algorithmic bytes / 8 TB/s exceeds executed f16 '
-                                  'FLOPs / dense f16 peak (fp32 operands as 2 f16 planes, 3 MFMAs per 16 k-values); '
-                                  'the matrix-pipe leg is in mfma_leg')
-      else:
-        roofline_split['hbm_leg'] = hbm_leg
-  # `roofline` is THE dominant kernel of the step, priced on the pipe it executes on; when that is a
-  # bf16-plane kernel the dominant fp32-MFMA kernel is kept beside it as `roofline_fp32`
-  roofline_fp32 = None
-  if roofline_split is not None and roofline_split['us_per_launch'] > roofline['us_per_launch']:
-    roofline_fp32, roofline = roofline, roofline_split
-  conv_us = sum(o['us'] for o in ops)
-  conv_gf = sum(o['gflop'] for o in ops)
-  stack = dict(us=round(conv_us, 1), gflop=round(conv_gf, 3),
-               tflops=round(conv_gf / conv_us * 1e3, 3),
-               frac=round(conv_gf / conv_us * 1e3 / PEAK_MFMA_F32_TFLOPS, 4))
-  hbm = profile_hbm_kernels(eng) if eng.in_shape[-1] in (1, 3) else [None]
-  mel_kernel = None
-  if kind == 'speech':
-    # the front-end launch alone (stft_mel_f64_kernel: float64 FFT + mel + dB, one workgroup per utterance):
-    # algorithmic bytes = the samples read once + the [B, T, n_mels] patch written once
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    for _ in range(5):
-      ex(y, out=xb)
-    torch.cuda.synchronize()
-    e0.record()
-    for _ in range(50):
-      ex(y, out=xb)
-    e1.record()
-    torch.cuda.synchronize()
-    t_mel = e0.elapsed_time(e1) / 50 * 1e-3
-    nbytes = 4.0 * y.numel() + 4.0 * xb.numel()
-    mel_kernel = dict(bound='hbm', kernel='stft_mel_db_frames (float64 STFT -> mel -> dB, unit range)',
-                      shape=[B, int(y.shape[1])], achieved=round(nbytes / t_mel * 1e-9, 1), peak=PEAK_HBM_GBS,
-                      unit='GB/s', frac=round(nbytes / t_mel * 1e-9 / PEAK_HBM_GBS, 4),
-                      us_per_launch=round(t_mel * 1e6, 2), mbytes_per_launch=round(nbytes * 1e-6, 2),
-                      note='compute-bound in float64 (the precision of the reference): B workgroups of 256 threads, '
-                           'n_fft 512: two radix-16 passes in registers, 16 lanes per frame (mel.hip); priced against HBM as north_star asks')
-  if args.profile_ops:
-    for o in ops:
-      print(f"# {o['layer']:14s} {o['op']:6s} {o['us']:9.1f} us {o['gflop']:8.3f} GF "
-            f"{o['tflops']:7.2f} TF/s  {o.get('path', '')}", file=sys.stderr)
-    print(f"# conv/dense stack: {stack}", file=sys.stderr)
-
-  # ---- CPU baseline: the same step as a torch-CPU fp32 port, all host cores --------------
-  cpu = None
-  if not args.no_cpu_baseline and world == 1:
-    from oracle.torch_ref import TorchFactorTrainer, TorchTrainer, TorchVAE
-    # torch-CPU scales to ~32 threads on this step (measured 8..128 on the GPU box's host:
-    # 32 is the fastest), so the baseline uses min(32, cores) threads and reports that count
-    cores = min(32, os.cpu_count() or 1)
-    torch.set_num_threads(cores)
-    model = TorchVAE(enc, dec, in_shape, zdim, observation=nets['observation'].posterior,
-                     beta=beta, tc_beta=beta if kind == 'betatc' else None, dtype=torch.float32)
-    P = {k: v.detach().cpu().numpy() for k, v in eng.param_views().items()}
-    n_cpu = args.cpu_steps
-    if kind == 'factor':
-      # both optimisers of one FactorVAE iteration (VAE step on 128 images with the discriminator's TC term,
-      # discriminator step on the other 128 + the permuted codes)
-      dp = fv._discriminator(B // 2).disc
-      DP = {k: v.detach().cpu().numpy() for k, v in dp.layout.views(dp.params).items()}
-      dlayers = [('dense', int(s2[1]), 'relu' if i + 1 < len(dp.recs) else 'linear')
-                 for i, (_, s2, _) in enumerate(e for e in dp.layout.entries if e[0][-1] == 'w')]
-      tr = TorchFactorTrainer(model, P, dlayers, DP, lr=lr, tc_coef=fv.tc_coef, threads=cores)
-      xc = x.cpu()
-      e1, e2 = torch.randn(B // 2, zdim), torch.randn(B // 2, zdim)
-      perm = torch.stack([torch.randperm(B // 2) for _ in range(zdim)], 1)
-      one = lambda: tr.step(xc, e1, e2, perm)
-      what = 'FactorVAE iterations (VAE step + discriminator step)'
-    elif kind == 'speech':
-      # the front-end on the host (numpy float64 restatement of odin/preprocessing/signal.py, the reference's
-      # own arithmetic) + the conv-VAE step
-      from oracle import mel_oracle as mo
-      tr = TorchTrainer(model, P, lr=lr, threads=cores)
-      yc = y.cpu().numpy().astype(np.float64)
-      ec = torch.randn(B, zdim)
-      T = in_shape[0]
-
-      def one():
-        # dB relative to the utterance's maximum, top_db = 80 -> [0, 1] (the mode-2 output of odin_stft_mel_db)
-        mel = np.stack([mo.mel_frontend(u)[:T] for u in yc])
-        mel = (mel - mel.max(axis=(1, 2), keepdims=True)) / 80.0 + 1.0
-        return tr.step(torch.tensor(mel.reshape(B, T, in_shape[1], 1), dtype=torch.float32), ec)
-      what = 'speech steps (numpy STFT -> mel -> dB front-end + conv-VAE step)'
-      n_cpu = max(2, args.cpu_steps // 8)
-    else:
-      tr = TorchTrainer(model, P, lr=lr, threads=cores)
-      xc, ec = x.cpu(), torch.randn(B, zdim)
-      one = lambda: tr.step(xc, ec)
-      what = 'training steps'
-    one()  # warm-up
-    c0 = time.perf_counter()
-    for _ in range(n_cpu):
-      one()
-    cdt = time.perf_counter() - c0
-    cpu = dict(value=round(B * n_cpu / cdt, 1), unit='images/sec', cores=cores,
-               kind='port', sample=f'{n_cpu} {what} of the same workload '
-               f'(batch {B}), torch-CPU fp32 port of the reference step')
-
-  ns3 = None
-  if world == 1 and args.workload == 'dsprites_betavae_b256' and not args.no_north_star_3ch:
-    ns3 = north_star_3ch(device)
-  fit_tp = None
-  if world == 1 and args.workload == 'dsprites_betavae_b256' and not args.no_fit:
-    fit_tp = fit_throughput(device)
-    for v in fit_tp.values():
-      v['frac_of_step_replay'] = round(v['images_per_sec'] / (B * args.steps / dt), 4)
-  exact = None
-  if world == 1 and args.workload == 'dsprites_betavae_b256' and not args.no_exact_fp32 and use_graph:
-    exact = exact_fp32_step(device)
-  # step-level HBM roofline: bytes of ALL launches of one step (PMC passes, committed table) / step time / 8 TB/s
-  hbm_step = None
-  ent = pmc.get('step')
-  if ent is not None and args.workload == 'dsprites_betavae_b256' and world == 1:
-    bps = ent['traffic_bytes']
-    hbm_step = dict(bytes_per_step=bps, launches=ent.get('launches'),
-                    achieved=round(bps / (dt / args.steps) * 1e-9, 1), peak=PEAK_HBM_GBS, unit='GB/s',
-                    frac=round(bps / (dt / args.steps) * 1e-9 / PEAK_HBM_GBS, 4),
-                    floor_ms=round(bps / (PEAK_HBM_GBS * 1e9) * 1e3, 4),
-                    source='profiles/' + os.path.basename(pmc_file), measured_in_this_run=False)
   res = dict(metric='VAE train images/sec', value=round(B * world * args.steps / dt, 1),
              unit='images/sec', n_gpus=world, steps=args.steps, warmup=args.warmup,
              ms_per_step=round(dt / args.steps * 1e3, 4), higher_is_better=True, scaling='weak',
@@ -1042,25 +891,217 @@ def main():
                                     'the f16 matrix pipe as 2 planes (x = h + 2^-11 l; 3 MFMAs per 16 k-values, fp32 '
                                     'accumulation, <= 3*2^-22 per product, gradient tensors scaled per tensor by an '
                                     'exact power of two), fp32 MFMA / VALU elsewhere (ODIN_EXACT_FP32=1: everywhere)',
-                         final_loss=round(loss, 4)),
-             roofline=roofline, roofline_split=roofline_split, roofline_fp32=roofline_fp32, cpu_baseline=cpu,
-             conv_stack=stack,
-             in_step_conv_frac=round(stack['gflop'] / (dt / args.steps) * 1e-3 / PEAK_MFMA_F32_TFLOPS, 4),
-             elbo_kernel=hbm[0],
-             elbo_kernel_b512=next((h for h in hbm if h and h['kernel'] == 'elbo_bernoulli_fwd_bwd' and
-                                    h['shape'] == [512, 64 * 64, 3]), None),
-             hbm_kernels=hbm,
-             north_star_3ch=ns3)
-  if exact is not None:
-    exact['headline_over_exact'] = round(exact['ms_per_step'] / (dt / args.steps * 1e3), 3)
-    res['exact_fp32'] = exact
-  if hbm_step is not None:
-    res['hbm'] = hbm_step
-  if fit_tp is not None:
-    res['fit_images_per_sec'] = fit_tp['device_dataset']['images_per_sec']
-    res['fit'] = fit_tp
-  if mel_kernel is not None:
-    res['mel_kernel'] = mel_kernel
+                         final_loss=round(loss, 4)))
+  if args.full:
+    # ---- roofline of the dominant kernel (per-launch, HIP events on the launch stream) ----
+    # Kernels whose path ends in "(bf16x3)" carry fp32 operands through the bf16 matrix pipe as three
+    # exact planes (6 bf16 MFMAs per 16 k-values): they are priced against the bf16 peak with the bf16
+    # FLOPs they execute (6 x the fp32 FLOPs of the convolution) in `roofline_split`;
+    # `roofline` is the dominant kernel among those that compute in fp32 MFMAs.
+    ops = profile_ops(eng)
+    is_split = lambda o: o.get('path', '').endswith('(f16x2)')
+    fp32_ops = [o for o in ops if not is_split(o)] or ops
+    dom = max(fp32_ops, key=lambda o: o['us'])
+    roofline = dict(bound='mfma', kernel=f"{dom['layer']}:{dom['op']}", path=dom.get('path'),
+                    achieved=round(dom['tflops'], 3), peak=PEAK_MFMA_F32_TFLOPS, unit='TFLOP/s',
+                    frac=round(dom['tflops'] / PEAK_MFMA_F32_TFLOPS, 4), traffic=None,
+                    us_per_launch=round(dom['us'], 2), gflop_per_launch=round(dom['gflop'], 4),
+                    note='fp32 FLOPs / dense fp32 MFMA peak (v_mfma_f32_16x16x4_f32 / 32x32x2_f32)')
+    pmc = {}
+    try:
+      import json as _json
+      import glob as _glob
+      # the newest round's PMC table (tools/pmc_traffic.py <tag> after tools/pmc.sh <tag>)
+      _cand = sorted(_glob.glob(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'profiles',
+                                             'r*_pmc_traffic.json')))
+      pmc_file = _cand[-1]
+      pmc = _json.load(open(pmc_file))
+    except (OSError, ValueError, IndexError):
+      pmc_file = None
+
+    def attach_traffic(obj):
+      # HBM traffic from the committed PMC passes (FETCH_SIZE / WRITE_SIZE cannot be collected inside
+      # this process); null when no measurement for this kernel on this workload is on file
+      ent = pmc.get(obj['kernel'])
+      if ent is not None and args.workload == 'dsprites_betavae_b256':
+        obj['traffic'] = ent['traffic_bytes']
+        obj['traffic_unit'] = 'bytes'
+        obj['algorithmic_bytes'] = ent.get('algorithmic_bytes')
+        obj['traffic_source'] = 'profiles/' + os.path.basename(pmc_file)
+        obj['traffic_measured_in_this_run'] = False  # (PMC counters cannot be collected inside this process)
+        if ent.get('us_in_graph'):
+          # what the STEP pays for this launch: its average duration inside the captured graph under rocprofv3
+          # (profiles/<round>_kernel_stats.csv), a few us longer than the stand-alone HIP-event time of this run
+          obj['us_in_graph'] = ent['us_in_graph']
+          obj['us_in_graph_source'] = ent.get('us_in_graph_source')
+          if ent.get('algorithmic_bytes'):
+            obj['frac_in_graph'] = round(ent['algorithmic_bytes'] / (ent['us_in_graph'] * 1e-6) * 1e-9 / PEAK_HBM_GBS, 4)
+
+    attach_traffic(roofline)
+    roofline_split = None
+    split_ops = [o for o in ops if is_split(o)]
+    if split_ops:
+      # A plane kernel executes 3 f16 MFMAs per 16 k-values (fp32 operands as two f16 planes): its matrix-pipe floor
+      # is executed FLOPs / the dense f16 peak, its memory floor algorithmic bytes / 8 TB/s.  Since the two-plane form
+      # the MEMORY floor is the higher one for the big layers (arithmetic intensity ~146 executed FLOP per byte against
+      # a machine balance of 314): the kernel is priced against the roof that binds it, the other leg is kept beside.
+      so = max(split_ops, key=lambda o: o['us'])
+      f16_gflop = 3.0 * so.get('mfma_gflop', so['gflop'])
+      mfma_leg = dict(achieved=round(f16_gflop / so['us'] * 1e3, 3), peak=PEAK_MFMA_BF16_TFLOPS,
+                      unit='TFLOP/s (f16 FLOPs executed)', frac=round(f16_gflop / so['us'] * 1e3 / PEAK_MFMA_BF16_TFLOPS, 4),
+                      gflop_per_launch=round(f16_gflop, 4),
+                      fp32_equivalent_tflops=round(so['tflops'], 3),
+                      fp32_equivalent_frac_of_fp32_mfma_peak=round(so['tflops'] / PEAK_MFMA_F32_TFLOPS, 4))
+      roofline_split = dict(bound='mfma', kernel=f"{so['layer']}:{so['op']}", path=so.get('path'), traffic=None,
+                            us_per_launch=round(so['us'], 2), **mfma_leg,
+                            note='fp32 operands as 2 f16 planes: 3 v_mfma_f32_32x32x16_f16 per 16 '
+                                 'k-values, priced against the dense f16 MFMA peak')
+      attach_traffic(roofline_split)
+      alg = roofline_split.get('algorithmic_bytes')
+      if alg:
+        t_hbm, t_mfma = alg / (PEAK_HBM_GBS * 1e9), f16_gflop * 1e9 / (PEAK_MFMA_BF16_TFLOPS * 1e12)
+        hbm_leg = dict(achieved=round(alg / (so['us'] * 1e-6) * 1e-9, 1), peak=PEAK_HBM_GBS, unit='GB/s',
+                       frac=round(alg / (so['us'] * 1e-6) * 1e-9 / PEAK_HBM_GBS, 4))
+        roofline_split['floors_us'] = dict(hbm=round(t_hbm * 1e6, 2), mfma=round(t_mfma * 1e6, 2))
+        if t_hbm >= t_mfma:
+          roofline_split.update(bound='hbm', mfma_leg=mfma_leg, **hbm_leg)
+          roofline_split['note'] = ('memory-bound by the roofline model: algorithmic bytes / 8 TB/s exceeds executed f16 '
+                                    'FLOPs / dense f16 peak (fp32 operands as 2 f16 planes, 3 MFMAs per 16 k-values); '
+                                    'the matrix-pipe leg is in mfma_leg')
+        else:
+          roofline_split['hbm_leg'] = hbm_leg
+    # `roofline` is THE dominant kernel of the step, priced on the pipe it executes on; when that is a
+    # bf16-plane kernel the dominant fp32-MFMA kernel is kept beside it as `roofline_fp32`
+    roofline_fp32 = None
+    if roofline_split is not None and roofline_split['us_per_launch'] > roofline['us_per_launch']:
+      roofline_fp32, roofline = roofline, roofline_split
+    conv_us = sum(o['us'] for o in ops)
+    conv_gf = sum(o['gflop'] for o in ops)
+    stack = dict(us=round(conv_us, 1), gflop=round(conv_gf, 3),
+                 tflops=round(conv_gf / conv_us * 1e3, 3),
+                 frac=round(conv_gf / conv_us * 1e3 / PEAK_MFMA_F32_TFLOPS, 4))
+    hbm = profile_hbm_kernels(eng) if eng.in_shape[-1] in (1, 3) else [None]
+    mel_kernel = None
+    if kind == 'speech':
+      # the front-end launch alone (stft_mel_f64_kernel: float64 FFT + mel + dB, one workgroup per utterance):
+      # algorithmic bytes = the samples read once + the [B, T, n_mels] patch written once
+      e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+      for _ in range(5):
+        ex(y, out=xb)
+      torch.cuda.synchronize()
+      e0.record()
+      for _ in range(50):
+        ex(y, out=xb)
+      e1.record()
+      torch.cuda.synchronize()
+      t_mel = e0.elapsed_time(e1) / 50 * 1e-3
+      nbytes = 4.0 * y.numel() + 4.0 * xb.numel()
+      mel_kernel = dict(bound='hbm', kernel='stft_mel_db_frames (float64 STFT -> mel -> dB, unit range)',
+                        shape=[B, int(y.shape[1])], achieved=round(nbytes / t_mel * 1e-9, 1), peak=PEAK_HBM_GBS,
+                        unit='GB/s', frac=round(nbytes / t_mel * 1e-9 / PEAK_HBM_GBS, 4),
+                        us_per_launch=round(t_mel * 1e6, 2), mbytes_per_launch=round(nbytes * 1e-6, 2),
+                        note='compute-bound in float64 (the precision of the reference): B workgroups of 256 threads, '
+                             'n_fft 512: two radix-16 passes in registers, 16 lanes per frame (mel.hip); priced against HBM as north_star asks')
+    if args.profile_ops:
+      for o in ops:
+        print(f"# {o['layer']:14s} {o['op']:6s} {o['us']:9.1f} us {o['gflop']:8.3f} GF "
+              f"{o['tflops']:7.2f} TF/s  {o.get('path', '')}", file=sys.stderr)
+      print(f"# conv/dense stack: {stack}", file=sys.stderr)
+
+    # ---- CPU baseline: the same step as a torch-CPU fp32 port, all host cores --------------
+    cpu = None
+    if not args.no_cpu_baseline and world == 1:
+      from oracle.torch_ref import TorchFactorTrainer, TorchTrainer, TorchVAE
+      # torch-CPU scales to ~32 threads on this step (measured 8..128 on the GPU box's host:
+      # 32 is the fastest), so the baseline uses min(32, cores) threads and reports that count
+      cores = min(32, os.cpu_count() or 1)
+      torch.set_num_threads(cores)
+      model = TorchVAE(enc, dec, in_shape, zdim, observation=nets['observation'].posterior,
+                       beta=beta, tc_beta=beta if kind == 'betatc' else None, dtype=torch.float32)
+      P = {k: v.detach().cpu().numpy() for k, v in eng.param_views().items()}
+      n_cpu = args.cpu_steps
+      if kind == 'factor':
+        # both optimisers of one FactorVAE iteration (VAE step on 128 images with the discriminator's TC term,
+        # discriminator step on the other 128 + the permuted codes)
+        dp = fv._discriminator(B // 2).disc
+        DP = {k: v.detach().cpu().numpy() for k, v in dp.layout.views(dp.params).items()}
+        dlayers = [('dense', int(s2[1]), 'relu' if i + 1 < len(dp.recs) else 'linear')
+                   for i, (_, s2, _) in enumerate(e for e in dp.layout.entries if e[0][-1] == 'w')]
+        tr = TorchFactorTrainer(model, P, dlayers, DP, lr=lr, tc_coef=fv.tc_coef, threads=cores)
+        xc = x.cpu()
+        e1, e2 = torch.randn(B // 2, zdim), torch.randn(B // 2, zdim)
+        perm = torch.stack([torch.randperm(B // 2) for _ in range(zdim)], 1)
+        one = lambda: tr.step(xc, e1, e2, perm)
+        what = 'FactorVAE iterations (VAE step + discriminator step)'
+      elif kind == 'speech':
+        # the front-end on the host (numpy float64 restatement of odin/preprocessing/signal.py, the reference's
+        # own arithmetic) + the conv-VAE step
+        from oracle import mel_oracle as mo
+        tr = TorchTrainer(model, P, lr=lr, threads=cores)
+        yc = y.cpu().numpy().astype(np.float64)
+        ec = torch.randn(B, zdim)
+        T = in_shape[0]
+
+        def one():
+          # dB relative to the utterance's maximum, top_db = 80 -> [0, 1] (the mode-2 output of odin_stft_mel_db)
+          mel = np.stack([mo.mel_frontend(u)[:T] for u in yc])
+          mel = (mel - mel.max(axis=(1, 2), keepdims=True)) / 80.0 + 1.0
+          return tr.step(torch.tensor(mel.reshape(B, T, in_shape[1], 1), dtype=torch.float32), ec)
+        what = 'speech steps (numpy STFT -> mel -> dB front-end + conv-VAE step)'
+        n_cpu = max(2, args.cpu_steps // 8)
+      else:
+        tr = TorchTrainer(model, P, lr=lr, threads=cores)
+        xc, ec = x.cpu(), torch.randn(B, zdim)
+        one = lambda: tr.step(xc, ec)
+        what = 'training steps'
+      one()  # warm-up
+      c0 = time.perf_counter()
+      for _ in range(n_cpu):
+        one()
+      cdt = time.perf_counter() - c0
+      cpu = dict(value=round(B * n_cpu / cdt, 1), unit='images/sec', cores=cores,
+                 kind='port', sample=f'{n_cpu} {what} of the same workload '
+                 f'(batch {B}), torch-CPU fp32 port of the reference step')
+
+    ns3 = None
+    if world == 1 and args.workload == 'dsprites_betavae_b256' and not args.no_north_star_3ch:
+      ns3 = north_star_3ch(device)
+    fit_tp = None
+    if world == 1 and args.workload == 'dsprites_betavae_b256' and not args.no_fit:
+      fit_tp = fit_throughput(device)
+      for v in fit_tp.values():
+        v['frac_of_step_replay'] = round(v['images_per_sec'] / (B * args.steps / dt), 4)
+    exact = None
+    if world == 1 and args.workload == 'dsprites_betavae_b256' and not args.no_exact_fp32 and use_graph:
+      exact = exact_fp32_step(device)
+    # step-level HBM roofline: bytes of ALL launches of one step (PMC passes, committed table) / step time / 8 TB/s
+    hbm_step = None
+    ent = pmc.get('step')
+    if ent is not None and args.workload == 'dsprites_betavae_b256' and world == 1:
+      bps = ent['traffic_bytes']
+      hbm_step = dict(bytes_per_step=bps, launches=ent.get('launches'),
+                      achieved=round(bps / (dt / args.steps) * 1e-9, 1), peak=PEAK_HBM_GBS, unit='GB/s',
+                      frac=round(bps / (dt / args.steps) * 1e-9 / PEAK_HBM_GBS, 4),
+                      floor_ms=round(bps / (PEAK_HBM_GBS * 1e9) * 1e3, 4),
+                      source='profiles/' + os.path.basename(pmc_file), measured_in_this_run=False)
+    res.update(roofline=roofline, roofline_split=roofline_split, roofline_fp32=roofline_fp32, cpu_baseline=cpu,
+               conv_stack=stack,
+               in_step_conv_frac=round(stack['gflop'] / (dt / args.steps) * 1e-3 / PEAK_MFMA_F32_TFLOPS, 4),
+               elbo_kernel=hbm[0],
+               elbo_kernel_b512=next((h for h in hbm if h and h['kernel'] == 'elbo_bernoulli_fwd_bwd' and
+                                      h['shape'] == [512, 64 * 64, 3]), None),
+               hbm_kernels=hbm,
+               north_star_3ch=ns3)
+    if exact is not None:
+      exact['headline_over_exact'] = round(exact['ms_per_step'] / (dt / args.steps * 1e3), 3)
+      res['exact_fp32'] = exact
+    if hbm_step is not None:
+      res['hbm'] = hbm_step
+    if fit_tp is not None:
+      res['fit_images_per_sec'] = fit_tp['device_dataset']['images_per_sec']
+      res['fit'] = fit_tp
+    if mel_kernel is not None:
+      res['mel_kernel'] = mel_kernel
   if rccl is not None:
     res['rccl'] = rccl
   print(json.dumps(res), file=json_out(), flush=True)

@@ -5,9 +5,10 @@ passes -- a kernel was renamed or rerouted and the table must be updated, not si
 HBM traffic per launch of the three largest kernels of the dsprites_betavae_b256 step, corrected as
 MI355X_MICROARCH.md prescribes (gfx950 FETCH_SIZE counts 128-byte reads at 64 bytes: doubled;
 WRITE_SIZE exact), next to the algorithmic bytes of the launch."""
-import json, re, sys
+import json, os, re, sys
 B = 256
 TAG = sys.argv[1] if len(sys.argv) > 1 else 'r06'
+OUT = os.environ.get('OUT', 'out')  # the folder tools/pmc.sh and tools/profile.sh wrote (relative to the repository root)
 
 
 COUNTS = {}  # file -> {(kernel, grid): dispatches in that pass} (the passes run different numbers of steps)
@@ -24,7 +25,7 @@ def read(fn):
   return out
 
 
-fetch, write = read(f'gpurun_out/{TAG}_pmc_FETCH_SIZE.txt'), read(f'gpurun_out/{TAG}_pmc_WRITE_SIZE.txt')
+fetch, write = read(f'{OUT}/{TAG}_pmc_FETCH_SIZE.txt'), read(f'{OUT}/{TAG}_pmc_WRITE_SIZE.txt')
 f4 = 4
 kernels = {
     # bench op name: (kernel-name prefix, grid, description, algorithmic bytes)
@@ -66,7 +67,7 @@ def find(tab, prefix, grid):
 def stats_us(prefix):
   """average in-graph duration (us) of the kernel from the rocprofv3 --stats table of the same run"""
   import csv, glob
-  for fn in glob.glob(f'gpurun_out/{TAG}_final_prof_kernel_stats.csv') + glob.glob(f'profiles/{TAG}_kernel_stats.csv'):
+  for fn in glob.glob(f'{OUT}/{TAG}_final_prof_kernel_stats.csv') + glob.glob(f'profiles/{TAG}_kernel_stats.csv'):
     for r in csv.DictReader(open(fn)):
       nm = r['Name'].replace('void ', '').replace('(anonymous namespace)::', '')
       if nm.startswith(prefix):
@@ -114,7 +115,7 @@ def lookup(tab, name, grid):
   return hits[0] if len(hits) == 1 else None
 
 
-TL = sys.argv[2] if len(sys.argv) > 2 else f'gpurun_out/{TAG}_final_prof_timeline.txt'
+TL = sys.argv[2] if len(sys.argv) > 2 else f'{OUT}/{TAG}_final_prof_timeline.txt'
 try:
   launches = step_launches(TL)
 except OSError:

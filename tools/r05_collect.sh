@@ -1,7 +1,7 @@
 #!/bin/bash
-# copies the outputs of tools/r05_final.sh (gpurun_out/, scratch) to their committed names under profiles/
+# copies the outputs of tools/r05_final.sh ($OUT/) to their committed names under profiles/
 cd "$(dirname "$0")/.."
-g=gpurun_out; p=profiles
+g=${OUT:-out}; p=profiles
 cp $g/r05_final_bench.json $p/r05_bench_default.json
 cp $g/r05_final_bench2.json $p/r05_bench_default_fresh_traffic.json
 cp $g/r05_final_per_op.txt $p/r05_bench_per_op.txt

@@ -3,7 +3,7 @@
 cd ${GRAFT_REPO_ROOT:-$(pwd)}
 mkdir -p gpurun_out
 timeout 600 python -m pytest tests/test_mel.py -q -m gpu 2>&1 | tail -3 > gpurun_out/r06_mel_tests.txt
-ab() { python bench.py --no-cpu-baseline --no-exact-fp32 --no-fit --no-north-star-3ch --workload speech_vae_b256 --profile-ops "$@" 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['ms_per_step'], d.get('mel_kernel'))"; }
+ab() { python bench.py --full --no-cpu-baseline --no-exact-fp32 --no-fit --no-north-star-3ch --workload speech_vae_b256 --profile-ops "$@" 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['ms_per_step'], d.get('mel_kernel'))"; }
 {
   for i in 1 2 3; do
     echo "speech r16          $(ab)"
