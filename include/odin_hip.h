@@ -424,6 +424,47 @@ int odin_total_correlation_fwd_bwd(const float* z, const float* p, float* tc_out
 int odin_total_correlation_shard(const float* z_local, const float* p_global, float* tc_out,
                                  float* dz_local, float* dloc_part, float* dscale_part,
                                  const float* coef, int B_local, int B_global, int D, void* stream);
+/* ---- InfoVAE's maximum-mean discrepancy (odin/bay/vi/losses.py:163-276 with q_sample_shape=None: the forward's
+ * sample x = z [N, D] against M prior samples y ~ N(0, I); info_vae.py:28-91) -- forward and backward in ONE launch.
+ * Biased estimator over all pairs, diagonal included: MMD = mean k(x,x) + mean k(y,y) - 2 mean k(x,y);
+ * kernel 0 = gaussian (k = exp(-|a-b|^2 / D), gaussian_kernel with sigma=None), 1 = linear (k = |sum_d (a_d - b_d)|,
+ * linear_kernel; its gradient takes sign(0) = 0).  ws[0] = coef[0] * MMD, dz = coef_grad[0] * dMMD/dx (k(y,y) enters
+ * the value only); coef / coef_grad: DEVICE scalars or NULL (1); dz NULL: forward only.  y NULL: drawn inside the
+ * launch as elements [0, M*D) of the stream odin_rng_normal(prior_seed, step_dev) writes -- bit for bit.  Cross-row
+ * sums in float64 in a fixed order, the workgroups' shares as 64-bit fixed-point words: bit-reproducible, no float
+ * atomics.  N <= 4096, D <= 64, M <= 512.  ws: odin_mmd_workspace(...) floats, 8-byte aligned, zeroed ONCE (every
+ * launch leaves it zeroed again). */
+int odin_mmd_workspace(int B_local, int B_global, int M, int D);
+int odin_mmd_fwd_bwd(const float* x, const float* y, float* ws, float* dz, const float* coef,
+                     const float* coef_grad, int N, int M, int D, int kernel, uint64_t prior_seed,
+                     const int32_t* step_dev, void* stream);
+/* The same with the rows sharded over ranks: this rank's rows x_local [B_local, D] against the all-gathered
+ * x_all [B_global, D] and y.  dz_local is complete (d/dx_i needs only x_i, every x_j and y); ws[0] = this rank's
+ * share of the value (sum the shares: all-reduce); include_yy: 1 on exactly one rank (the k(y,y) term).  y must be
+ * the same on every rank: prior_seed must not depend on the rank. */
+int odin_mmd_shard(const float* x_local, const float* x_all, const float* y, float* ws, float* dz_local,
+                   const float* coef, const float* coef_grad, int B_local, int B_global, int M, int D,
+                   int kernel, int include_yy, uint64_t prior_seed, const int32_t* step_dev, void* stream);
+/* ---- DIPVAE's disentangled-inferred-prior penalty (odin/bay/vi/losses.py:39-98; dip_vae.py) on p [N, 2D]:
+ * loc = p[:, :D], scale = softplus(p[:, D:]).  Cov = centred biased covariance of loc over the N rows
+ * (+ diag(mean scale^2) for type II, type2 = 1: only_mean=False); value = lambda_offdiag * sum_{k!=l} Cov_kl^2 +
+ * lambda_diag * sum_k (Cov_kk - 1)^2.  ws[0] = coef[0] * value; with G = dvalue/dCov: dloc_i = coef_grad[0] *
+ * (2/N) G (loc_i - mean), dscale_ik = coef_grad[0] * G_kk * 2 scale_ik / N (zeros for type I); dloc / dscale NULL:
+ * not written.  ONE launch (one workgroup: float64 sums in a fixed order).  D <= 64.
+ * ws: odin_dip_workspace(world, D) floats. */
+int odin_dip_workspace(int world, int D);
+int odin_dip_fwd_bwd(const float* p, float* ws, float* dloc, float* dscale, const float* coef,
+                     const float* coef_grad, int N, int D, int type2, float lambda_diag, float lambda_offdiag,
+                     void* stream);
+/* Data parallel: odin_dip_moments writes this rank's moment block [n | mean[D] | centred M2[D][D] | sum scale^2 [D]]
+ * (1 + 2D + D*D floats; ws + 4 of the workspace); the blocks of all ranks are all-gathered (rank order) and
+ * odin_dip_finish combines them in rank order (Chan et al.'s pairwise update: no raw E[mu mu^T] - E[mu]E[mu]^T
+ * cancellation), writes ws[0] = coef[0] * value -- the whole batch's, the same on every rank -- and this rank's
+ * dloc / dscale. */
+int odin_dip_moments(const float* p_local, float* block, int B_local, int D, void* stream);
+int odin_dip_finish(const float* blocks, int world, const float* p_local, float* ws, float* dloc,
+                    float* dscale, const float* coef, const float* coef_grad, int B_local, int D, int type2,
+                    float lambda_diag, float lambda_offdiag, void* stream);
 /* permute_dims (odin/bay/vi/utils.py:233-269): out[i,l] = z[perm[i,l], l]; perm int32 [B,D] */
 int odin_permute_dims(const float* z, const int32_t* perm, float* out, int B, int D, void* stream);
 /* per-column random permutations generated on device (Philox), perm int32 [B,D] */

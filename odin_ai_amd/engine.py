@@ -441,6 +441,8 @@ def observation_maps(observation: str, C: int) -> int:
 H_ALPHA, H_B1, H_B2, H_EPS, H_GSCALE, H_INVB, H_KLW, H_BETA, H_TCCOEF, H_TCGRAD = range(10)
 H_CAP = 15  # BetaCapacityVAE: the capacity C(step) (slots 10..14: the second optimiser's Adam block)
 N_HYPER = 16
+MMD_KERNELS = {'gaussian': 0, 'linear': 1}   # odin_mmd_fwd_bwd's `kernel`
+PRIOR_KEY_SALT = 0x6D6D6470 << 32            # high word of the prior stream's Philox key (eps streams: seed < 2^32)
 
 
 class VAEEngine:
@@ -448,6 +450,7 @@ class VAEEngine:
 
   observation: 'bernoulli' | 'gaussian' | 'gaussian_softplus1' | 'qlogistic' | 'mixqlogistic'
   tc: None | 'betatc' (total_correlation, weight (beta-1))
+  latent_reg: None | 'mmd' | 'dip_i' | 'dip_ii' (InfoVAE's maximum-mean discrepancy / DIPVAE's penalty, weight reg_coef)
   """
 
   def __init__(self, enc_layers, dec_layers, in_shape, zdim, batch_size, device,
@@ -459,7 +462,9 @@ class VAEEngine:
                act_words: bool = True, hyper_ring: bool = True, hyper_ring_rows: int = 128, fuse_norm: bool = True,
                overlap_wgrad: Optional[str] = None, early_reduce: bool = False, defer_wgrad: bool = False,
                side_streams: int = 2, small_wgrad_gf: float = 0.8, dp_buckets: Optional[int] = None,
-               neck: bool = True, neck_bwd: Optional[bool] = None, static_top_word: bool = True):
+               neck: bool = True, neck_bwd: Optional[bool] = None, static_top_word: bool = True,
+               latent_reg: Optional[str] = None, reg_coef: float = 1.0, mmd_kernel: str = 'gaussian',
+               mmd_prior_samples: int = 100, dip_lambda: Tuple[float, float] = (1.0, 2.0), prior_seed: int = 0):
     """The keyword-only arguments are the engine's launch-order / A-B options (tests and tools pass them; the engine
     reads no environment variable):
       act_words        activation range words for the two-plane consumers; False: unscaled planes
@@ -478,7 +483,16 @@ class VAEEngine:
       neck             the encoder's last convolution + projection + latent block + the decoder's projection + first
                        Conv2DTranspose as ONE launch per direction where the shapes allow (neck.hip); False: round 5's
                        four launches per direction
-      neck_bwd         the neck's backward launch (None: where it was measured faster)"""
+      neck_bwd         the neck's backward launch (None: where it was measured faster)
+    The batch regularisers of InfoVAE / DIPVAE (latent_reg.hip; not combinable with `tc`):
+      latent_reg         None | 'mmd' (maximum_mean_discrepancy of z against the prior) | 'dip_i' / 'dip_ii'
+                         (disentangled_inferred_prior_loss with only_mean True / False); the term reg_coef * value is
+                         added to the loss and reported as out4[3]
+      reg_coef           its weight (H_TCCOEF / H_TCGRAD; set_hyper(reg_coef=) overrides it per step)
+      mmd_kernel         'gaussian' | 'linear'
+      mmd_prior_samples  M prior samples per step, drawn on the device from (prior_seed, step)
+      dip_lambda         (lambda_diag, lambda_offdiag)
+      prior_seed         key of the prior sample's stream: must be the same on every rank (unlike `seed`)"""
     self.lib = lib if lib is not None else _lib.load()
     self.device = torch.device(device)
     self.B, self.D = int(batch_size), int(zdim)
@@ -497,6 +511,14 @@ class VAEEngine:
     # beta-TC: the global-batch estimator (all-gather | shard kernel | reduce-scatter) whenever the step is
     # data parallel -- also at world size 1 under `force_dp`, which is how a 1-GPU box exercises it
     self.tc_sharded = tc == 'betatc' and self.is_dp
+    if latent_reg not in (None, 'mmd', 'dip_i', 'dip_ii'):
+      raise ValueError(f"latent_reg={latent_reg!r}: expected None, 'mmd', 'dip_i' or 'dip_ii'")
+    if latent_reg is not None and tc is not None:
+      raise ValueError(f'latent_reg={latent_reg!r} cannot be combined with tc={tc!r}')
+    if latent_reg == 'mmd' and mmd_kernel not in MMD_KERNELS:
+      raise NotImplementedError(f'mmd_kernel={mmd_kernel!r}: the HIP path offers {sorted(MMD_KERNELS)}')
+    self.reg_mode, self.reg_coef = latent_reg, float(reg_coef)
+    self.reg_sharded = latent_reg is not None and self.is_dp
     f32 = dict(dtype=torch.float32, device=self.device)
     # ---- parameters ----
     self.layout = ParamLayout()
@@ -602,6 +624,8 @@ class VAEEngine:
         self.tc_pz_all = torch.empty(Bg, 3 * D, **f32)
         self.tc_p_all = torch.empty(Bg, 2 * D, **f32)
         self.tc_part_all = torch.empty(2, Bg, D, **f32)    # dloc / dscale partials for every i
+    if latent_reg is not None:
+      self._plan_latent_reg(f32, mmd_kernel, mmd_prior_samples, dip_lambda, prior_seed)
     self._plan_fused_tail(f32)
     self._plan_gauss_head(f32)
     self._plan_latent_block(f32)
@@ -675,6 +699,28 @@ class VAEEngine:
     big = self.grads.numel() * 4 >= (8 << 20)
     self.dp_buckets = int(dp_buckets or 0) or (2 if (self.world_size >= 4 and big) else 1)
     self.dec_start = min(o for k, _, o in self.layout.entries if k[0] == 'dec')
+
+  def _plan_latent_reg(self, f32, mmd_kernel, M, dip_lambda, prior_seed):
+    B, D, W = self.B, self.D, self.world_size
+    if self.reg_mode == 'mmd':
+      self.mmd_kernel, self.mmd_M = MMD_KERNELS[mmd_kernel], int(M)
+      # (the prior stream's key: the high word is offset so that it never meets an eps stream keyed by a seed < 2^32)
+      self.prior_key = (int(prior_seed) ^ PRIOR_KEY_SALT) & 0xFFFFFFFFFFFFFFFF
+      self.reg_ws = torch.zeros(self.lib.odin_mmd_workspace(B, B * W, self.mmd_M, D), **f32)
+      self.reg_dz = torch.empty(B, D, **f32)
+      self.reg_y = torch.zeros(self.mmd_M, D, **f32)   # an explicit prior sample (forward(..., prior=y))
+      if self.reg_sharded:
+        self.reg_z_all = torch.empty(B * W, D, **f32)
+    else:
+      self.dip_type2 = int(self.reg_mode == 'dip_ii')
+      self.dip_lambda = (float(dip_lambda[0]), float(dip_lambda[1]))
+      self.reg_ws = torch.zeros(self.lib.odin_dip_workspace(W, D), **f32)
+      self.reg_dloc = torch.empty(B, D, **f32)
+      self.reg_dscale = torch.empty(B, D, **f32)
+      bs = 1 + 2 * D + D * D
+      self.dip_block_local = self.reg_ws[4:4 + bs]
+      self.dip_blocks = self.reg_ws[4 + bs:4 + bs + W * bs]
+    self._prior_explicit = False
 
   def _comm(self):
     if self.comm is None:
@@ -943,7 +989,7 @@ class VAEEngine:
   def set_hyper(self, lr=1e-3, beta=1.0, b1=0.9, b2=0.999, eps=1e-7, grad_scale=1.0,
                 t: Optional[int] = None, tc_coef: Optional[float] = None,
                 skip_enable: bool = True, extra: Optional[Sequence[float]] = None,
-                capacity: Optional[float] = None):
+                capacity: Optional[float] = None, reg_coef: Optional[float] = None):
     """Host scalars -> device (one small async H2D copy)."""
     t = self.step_count if t is None else t
     self._ring_live = False   # (an explicit copy: whatever the ring predicted for this step no longer counts)
@@ -952,7 +998,7 @@ class VAEEngine:
     if self._ring_ev[self._ring_i] is not None:
       self._ring_ev[self._ring_i].synchronize()
     self._fill_row(h, t, lr=lr, beta=beta, b1=b1, b2=b2, eps=eps, grad_scale=grad_scale, tc_coef=tc_coef,
-                   skip_enable=skip_enable, extra=extra, capacity=capacity)
+                   skip_enable=skip_enable, extra=extra, capacity=capacity, reg_coef=reg_coef)
     # (leaving this 80-byte copy out of the steady state was measured in round 4 at 0.72 ms per step: no difference;
     # at 0.52 ms it is worth 7-8 us -- profiles/r05_hyper_ring.txt -- hence the device ring of train_step)
     self.hyper.copy_(h, non_blocking=True)
@@ -962,7 +1008,7 @@ class VAEEngine:
       self._ring_ev[self._ring_i] = ev
 
   def _fill_row(self, h, t, lr=1e-3, beta=1.0, b1=0.9, b2=0.999, eps=1e-7, grad_scale=1.0, tc_coef=None,
-                skip_enable=True, extra=None, capacity=None):
+                skip_enable=True, extra=None, capacity=None, reg_coef=None):
     """the hyper-parameter row of step t into the host tensor h (N_HYPER + 4 floats)"""
     tt = max(int(t), 1)
     Bg = self.B * self.world_size
@@ -978,6 +1024,10 @@ class VAEEngine:
     h[H_TCGRAD] = (beta - 1.0) if self.tc_mode == 'betatc' else 0.0
     if tc_coef is not None:  # FactorVAE: tc term = tc_coef * mean(D(z))
       h[H_TCCOEF] = tc_coef
+    if self.reg_mode is not None:
+      # InfoVAE / DIPVAE: the term reg_coef * value; every rank back-propagates the full d(value)/d(its own rows), as
+      # for beta-TC
+      h[H_TCCOEF] = h[H_TCGRAD] = self.reg_coef if reg_coef is None else float(reg_coef)
     if extra is not None:  # second optimiser's Adam block (FactorVAE discriminator), slots 10..14
       for i, val in enumerate(extra):
         h[10 + i] = float(val)
@@ -1140,14 +1190,21 @@ class VAEEngine:
   # ---- forward -----------------------------------------------------------------------
   def forward(self, x: torch.Tensor, eps: Optional[torch.Tensor] = None, st=None,
               fused: bool = True, tc_ptr: Optional[int] = None, finalize: bool = True,
-              tc_split: bool = False, after_latent=None):
+              tc_split: bool = False, after_latent=None, prior: Optional[torch.Tensor] = None):
     """Runs encode -> reparameterise -> decode -> ELBO (+ dlogits).  `eps=None` draws the
-    noise on device from the Philox stream (seed, step).  `after_latent()` (optional) is called once z is issued
+    noise on device from the Philox stream (seed, step); `prior` [M, D] (latent_reg='mmd'): an explicit prior sample
+    instead of the one drawn from (prior_seed, step).  `after_latent()` (optional) is called once z is issued
     on the stream -- FactorVAE forks its discriminator pass onto a side stream there, beside the decoder."""
     lib, B, D = self.lib, self.B, self.D
     st = self.stream() if st is None else st
     assert x.shape == (B,) + self.in_shape and x.is_contiguous()
     self.x = x
+    if self.reg_mode == 'mmd':
+      self._prior_explicit = prior is not None
+      if prior is not None and prior is not self.reg_y:
+        self.reg_y.copy_(prior.reshape(self.reg_y.shape))
+    else:
+      assert prior is None, 'an explicit prior sample needs latent_reg="mmd"'
     lw = self.params[self.lat_w_off:]
     lb = self.params[self.lat_b_off:]
     self._used_block = self.lat_block and fused
@@ -1271,6 +1328,12 @@ class VAEEngine:
       self._tc_pack()
       self._llk_part_used = llk_part
       return h_d
+    if self.reg_sharded and tc_split:
+      # the same for the InfoVAE / DIPVAE regulariser (step_program: _reg_segments)
+      if self.reg_mode != 'mmd':
+        self._dip_moments(st)
+      self._llk_part_used = llk_part
+      return h_d
     if self.tc_sharded:
       self._tc_pack()
       self._tc_gather()
@@ -1283,6 +1346,22 @@ class VAEEngine:
                                          self.tc_dloc.data_ptr(), self.tc_dscale.data_ptr(),
                                          self.hp(H_TCGRAD), B, D, st)
       tcp = self.tc_ws.data_ptr()
+    elif self.reg_sharded:
+      if self.reg_mode != 'mmd':
+        self._dip_moments(st)
+      for kind, fn in self._reg_segments():
+        fn()
+      tcp = self.reg_ws.data_ptr()
+    elif self.reg_mode == 'mmd':
+      lib.odin_mmd_fwd_bwd(self.z.data_ptr(), self._prior_ptr(), self.reg_ws.data_ptr(), self.reg_dz.data_ptr(),
+                           None, self.hp(H_TCGRAD), B, self.mmd_M, D, self.mmd_kernel, self.prior_key,
+                           self.hp(N_HYPER), st)
+      tcp = self.reg_ws.data_ptr()
+    elif self.reg_mode is not None:
+      lib.odin_dip_fwd_bwd(self.p.data_ptr(), self.reg_ws.data_ptr(), self.reg_dloc.data_ptr(),
+                           self.reg_dscale.data_ptr() if self.dip_type2 else None, None, self.hp(H_TCGRAD), B, D,
+                           self.dip_type2, self.dip_lambda[0], self.dip_lambda[1], st)
+      tcp = self.reg_ws.data_ptr()
     self._llk_part_used = llk_part
     if tc_ptr is not None:
       tcp = tc_ptr
@@ -1318,6 +1397,38 @@ class VAEEngine:
     c.reduce_scatter(self.tc_dloc.view(-1), self.tc_part_all[0].view(-1))
     c.reduce_scatter(self.tc_dscale.view(-1), self.tc_part_all[1].view(-1))
     c.all_reduce(self.tc_ws[:1])
+
+  # InfoVAE / DIPVAE under data parallelism (the regulariser couples the GLOBAL batch):
+  #   MMD: all-gather z | shard kernel (this rank's rows against every row and the prior; dz complete) | all-reduce
+  #        of the value shares;
+  #   DIP: moment block of this rank's rows (in forward) | all-gather of the blocks | finish (the same value on every
+  #        rank, this rank's dloc / dscale).
+  def _prior_ptr(self):
+    return self.reg_y.data_ptr() if self._prior_explicit else None
+
+  def _dip_moments(self, st=None):
+    st = self.stream() if st is None else st
+    self.lib.odin_dip_moments(self.p.data_ptr(), self.dip_block_local.data_ptr(), self.B, self.D, st)
+
+  def _reg_segments(self):
+    """the regulariser's pieces after forward(tc_split=True): [('c' | 'k', fn)]"""
+    lib, B, D, W = self.lib, self.B, self.D, self.world_size
+    c = self._comm
+    if self.reg_mode == 'mmd':
+      def shard():
+        rank = c().rank
+        lib.odin_mmd_shard(self.z.data_ptr(), self.reg_z_all.data_ptr(), self._prior_ptr(), self.reg_ws.data_ptr(),
+                           self.reg_dz.data_ptr(), None, self.hp(H_TCGRAD), B, B * W, self.mmd_M, D, self.mmd_kernel,
+                           int(rank == 0), self.prior_key, self.hp(N_HYPER), self.stream())
+      return [('c', lambda: c().all_gather(self.reg_z_all.view(-1), self.z.view(-1))),
+              ('k', shard),
+              ('c', lambda: c().all_reduce(self.reg_ws[:1]))]
+
+    def finish():
+      lib.odin_dip_finish(self.dip_blocks.data_ptr(), W, self.p.data_ptr(), self.reg_ws.data_ptr(),
+                          self.reg_dloc.data_ptr(), self.reg_dscale.data_ptr() if self.dip_type2 else None, None,
+                          self.hp(H_TCGRAD), B, D, self.dip_type2, self.dip_lambda[0], self.dip_lambda[1], self.stream())
+    return [('c', lambda: c().all_gather(self.dip_blocks, self.dip_block_local)), ('k', finish)]
 
   def finalize(self, tc_ptr: Optional[int] = None, st=None):
     st = self.stream() if st is None else st
@@ -1424,6 +1535,12 @@ class VAEEngine:
       dzx = self.tc_dz.data_ptr()
     tl = self.tc_dloc.data_ptr() if self.tc_mode == 'betatc' else None
     ts = self.tc_dscale.data_ptr() if self.tc_mode == 'betatc' else None
+    if self.reg_mode == 'mmd':
+      assert extra_dz is None
+      dzx = self.reg_dz.data_ptr()
+    elif self.reg_mode is not None:
+      tl = self.reg_dloc.data_ptr()
+      ts = self.reg_dscale.data_ptr() if self.dip_type2 else None
     h_e = self.enc.outs[-1]
     last = self.enc_recs[-1]
     aux_act = ACT[last.act]
@@ -1618,7 +1735,7 @@ class VAEEngine:
       self._comm().all_reduce(self.grads[lo:hi])
 
   # ---- one optimisation step ---------------------------------------------------------
-  def step_program(self, x, eps, pol):
+  def step_program(self, x, eps, pol, prior=None):
     """The launch program of one step: [('k', fn) kernels | ('c', fn) collective].  Single GPU: all
     kernels.  Data parallel: ... backward | all-reduce | update, with the decoder's gradient bucket
     reduced on a side stream beside the encoder's backward pass when dp_buckets == 2; beta-TC under
@@ -1631,12 +1748,17 @@ class VAEEngine:
       P.append(('k', self._tc_shard))
       P.append(('c', self._tc_scatter))
       P.append(('k', lambda: self.finalize(self.tc_ws.data_ptr())))
+    elif self.reg_sharded:
+      P.append(('k', lambda: self.forward(x, eps, tc_split=True, prior=prior)))
+      P += self._reg_segments()
+      P.append(('k', lambda: self.finalize(self.reg_ws.data_ptr())))
     else:
       # the ELBO finalisation (llk[B], loss, mean terms: nothing in the backward pass reads them) rides in the
       # update's first launch instead of being a launch of its own
       def fwd():
-        self.forward(x, eps, finalize=False)
-        tcp = self.tc_ws.data_ptr() if self.tc_mode == 'betatc' else None
+        self.forward(x, eps, finalize=False, prior=prior)
+        tcp = (self.tc_ws.data_ptr() if self.tc_mode == 'betatc' else
+               self.reg_ws.data_ptr() if self.reg_mode is not None else None)
         self._fin_pending = (self._llk_part_used.data_ptr(), self.n_part, tcp)
       P.append(('k', fwd))
     if self.is_dp and self.dp_buckets >= 2:
@@ -1679,23 +1801,30 @@ class VAEEngine:
                  global_clipnorm: Optional[float] = None, use_graph: bool = False,
                  clipnorm: Optional[float] = None, clipvalue: Optional[float] = None,
                  skip_update_threshold: Optional[float] = None, when_skip_update: int = 0,
-                 check_nan: bool = True, capacity: Optional[float] = None, schedule=None):
+                 check_nan: bool = True, capacity: Optional[float] = None, schedule=None,
+                 prior: Optional[torch.Tensor] = None, reg_coef: Optional[float] = None):
     """Networks.optimize for one VAEStep: step += 1, forward, backward, (all-reduce), gradient
     policies, Adam.  Returns the device tensor out4 = [loss, mean llk, mean beta*kl, tc] (no host
-    sync)."""
+    sync).  `prior` (latent_reg='mmd'): an explicit prior sample [M, D] for this step; `reg_coef`: the regulariser's
+    weight for this step (default: the constructor's)."""
     self.step_count += 1
     # the device ring serves the update path whose last two launches are odin_sumsq_adam_ring (norm + Adam)
     ring = bool(self.use_hyper_ring and clipvalue is None and (global_clipnorm is not None or check_nan))
     if ring:
-      self._ring_step(self.step_count, dict(lr=lr, beta=beta, when_skip_update=int(when_skip_update),
-                                            capacity=capacity), schedule)
+      args = dict(lr=lr, beta=beta, when_skip_update=int(when_skip_update), capacity=capacity)
+      if reg_coef is not None:
+        args['reg_coef'] = reg_coef
+      self._ring_step(self.step_count, args, schedule)
     else:
-      self.set_hyper(lr=lr, beta=beta, skip_enable=self.step_count >= int(when_skip_update), capacity=capacity)
+      self.set_hyper(lr=lr, beta=beta, skip_enable=self.step_count >= int(when_skip_update), capacity=capacity,
+                     reg_coef=reg_coef)
     pol = (global_clipnorm, clipnorm, clipvalue, skip_update_threshold, bool(check_nan), ring)
+    if prior is not None:
+      assert self.reg_mode == 'mmd', 'an explicit prior sample needs latent_reg="mmd"'
     if use_graph and self.device.type == 'cuda':
-      self._graph_step(x, eps, pol)
+      self._graph_step(x, eps, pol, prior)
     else:
-      for _, fn in self.step_program(x, eps, pol):
+      for _, fn in self.step_program(x, eps, pol, prior):
         fn()
     return self.out4
 
@@ -1712,7 +1841,7 @@ class VAEEngine:
       self.x_static = torch.empty((self.B,) + self.in_shape, dtype=torch.float32, device=self.device)
     return self.x_static
 
-  def _graph_step(self, x, eps, pol):
+  def _graph_step(self, x, eps, pol, prior=None):
     """Capture the step once into HIP graphs, replay afterwards.  Single GPU: ONE graph (forward +
     backward + slab reduction + policies + Adam).  Data parallel: the kernel segments of
     `step_program` as one graph each, the RCCL collectives between them eager on the same stream
@@ -1723,6 +1852,8 @@ class VAEEngine:
     silently replaying the old one."""
     from .dist import SegmentedGraph
     key = (pol, self.analytic, self.free_bits, eps is not None, self.dp_buckets)
+    if prior is not None:   # (an explicit prior sample: a graph of its own that reads reg_y)
+      key = key + ('prior',)
     if not hasattr(self, '_graphs'):
       self._graphs = {}
     if key not in self._graphs:
@@ -1732,7 +1863,10 @@ class VAEEngine:
       if eps is not None:
         self.eps.copy_(eps)
       ex = eps is not None
-      sg = SegmentedGraph(self.device, self.step_program(self.x_static, self.eps if ex else None, pol))
+      if prior is not None:
+        self.reg_y.copy_(prior.reshape(self.reg_y.shape))
+      sg = SegmentedGraph(self.device, self.step_program(self.x_static, self.eps if ex else None, pol,
+                                                         self.reg_y if prior is not None else None))
       # warm-up outside capture (first-call attribute setup, lazy allocations, communicator set-up)
       cap = torch.cuda.Stream(self.device)
       cap.wait_stream(torch.cuda.current_stream(self.device))
@@ -1755,4 +1889,6 @@ class VAEEngine:
       self.x_static.copy_(x, non_blocking=True)
     if eps is not None:
       self.eps.copy_(eps, non_blocking=True)
+    if prior is not None:
+      self.reg_y.copy_(prior.reshape(self.reg_y.shape), non_blocking=True)
     sg.replay()

@@ -1,4 +1,4 @@
-"""VariationalAutoencoder / BetaVAE / AnnealingVAE / BetaTCVAE / FactorVAE on the HIP engine.
+"""VariationalAutoencoder / BetaVAE / AnnealingVAE / BetaTCVAE / FactorVAE / InfoVAE / DIPVAE on the HIP engine.
 
 Drop-in for the reference's model API on this path (same class names, constructor
 arguments, method names, returned structures and error behaviour):
@@ -7,6 +7,8 @@ arguments, method names, returned structures and error behaviour):
   odin/bay/vi/_base.py:21-194                             (ELBO configuration, elbo())
   odin/bay/vi/autoencoder/beta_vae.py:11,83,110           (BetaVAE, AnnealingVAE, BetaTCVAE)
   odin/bay/vi/autoencoder/factor_vae.py:99                (FactorVAE, two-step training)
+  odin/bay/vi/autoencoder/info_vae.py:28-91               (InfoVAE: maximum-mean discrepancy)
+  odin/bay/vi/autoencoder/dip_vae.py                      (DIPVAE: disentangled inferred prior)
   odin/networks/base_networks.py:415-812                  (optimize(), fit())
 
 Tensors are torch tensors on the model's device; returned "distributions" are light
@@ -17,6 +19,7 @@ backward / Adam runs in libodin_hip.so through ``VAEEngine``.
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import math
 import os
 from dataclasses import dataclass, field
@@ -29,6 +32,7 @@ from . import _lib
 from .engine import (ACT, H_ALPHA, N_HYPER, RANGE_WORDS, NetProgram, ParamLayout, ReduceJob, VAEEngine,
                      build_layers)
 from .interpolation import Interpolation, linear
+from .losses import disentangled_inferred_prior_loss, maximum_mean_discrepancy, mmd_config
 from .networks import RVconf, SequentialNetwork, get_networks, layer_names
 
 LOG2PI = math.log(2.0 * math.pi)
@@ -379,7 +383,7 @@ class VariationalAutoencoder:
                       lib=self._lib, params=self._params, seed=self.seed + self._rank(),
                       optim_state=self._optim_state, world_size=self._world_size(),
                       force_dp=bool(getattr(self, 'force_dp', False)),
-                      **getattr(self, 'engine_options', {}))
+                      **self._reg_options(), **getattr(self, 'engine_options', {}))
       if self._params is None:
         self._params = eng.params
         self._optim_state = (eng.m, eng.v)
@@ -476,6 +480,12 @@ class VariationalAutoencoder:
     """per-step scalars beyond (lr, beta) that a subclass hands to the engine (BetaCapacityVAE: the capacity)"""
     return {}
 
+  # the batch regulariser of InfoVAE / DIPVAE: engine options and the key of its term in `kl` / the metrics
+  _reg_key: Optional[str] = None
+
+  def _reg_options(self) -> dict:
+    return {}
+
   # ------------------------------------------------------------------ forward API
   def _posterior(self, eng: VAEEngine) -> MVNDiagPosterior:
     return MVNDiagPosterior(eng.p.clone(), eng.z.clone(), eng.D)
@@ -536,6 +546,8 @@ class VariationalAutoencoder:
     kl = {f'kl_{self.latents.name}': klv}
     if self._tc_mode == 'betatc':
       kl[f'tc_{self.latents.name}'] = (self.beta - 1.0) * eng.tc_ws[0].clone()
+    if self._reg_key is not None:   # reg_coef * value, the term the loss carries (NOT multiplied by beta)
+      kl[f'{self._reg_key}_{self.latents.name}'] = eng.out4[3].clone()
     return llk, kl
 
   def elbo(self, llk: Dict[str, torch.Tensor], kl: Dict[str, torch.Tensor]) -> torch.Tensor:
@@ -657,6 +669,8 @@ class VariationalAutoencoder:
     metrics = {f'llk_{self.observation.name}': out[1], f'kl_{self.latents.name}': out[2]}
     if self._tc_mode == 'betatc':
       metrics[f'tc_{self.latents.name}'] = out[3]
+    if self._reg_key is not None:
+      metrics[f'{self._reg_key}_{self.latents.name}'] = out[3]
     if training and track_gradients:
       for k, g in eng.grad_views().items():
         metrics['_grad/' + self.variable_name(k)] = g.clone()
@@ -993,6 +1007,63 @@ class BetaTCVAE(BetaVAE):
     super().__init__(beta=beta, name=name, **kwargs)
     self._tc_mode = 'betatc'
     self._engines.clear()
+
+
+class InfoVAE(BetaVAE):
+  """info_vae.py:28-91: a BetaVAE with beta = 1 - alpha plus kl['div_<latents>'] = (lamda - beta) * MMD(q(z), p(z))
+  (losses.py:222-276), added after BetaVAE scales the KL -- not multiplied by beta.  The MMD reuses the forward's
+  sample (q_sample_shape=None) against p_sample_shape prior samples drawn on the device every step; its value and its
+  gradient come from one launch per step (latent_reg.hip).  `divergence`: a functools.partial of
+  maximum_mean_discrepancy; anything else the HIP path does not compute (another callable, q_sample_shape other than
+  None, kernel='polynomial') raises NotImplementedError.  A `beta=` keyword is accepted and discarded, as the
+  reference pops it."""
+
+  def __init__(self, alpha: float = 0.0, lamda: float = 100.0,
+               divergence: Callable = functools.partial(maximum_mean_discrepancy, kernel='gaussian',
+                                                        q_sample_shape=None, p_sample_shape=100),
+               name='InfoVAE', **kwargs):
+    kwargs.pop('beta', None)
+    if not callable(divergence):
+      raise AssertionError(f'divergence must be callable, but given: {type(divergence)}')
+    self.mmd_kernel, self.mmd_prior_samples = mmd_config(divergence)
+    self.divergence = divergence
+    self.lamda = float(lamda)
+    super().__init__(beta=1.0 - float(alpha), name=name, **kwargs)
+
+  @property
+  def alpha(self) -> float:
+    return 1.0 - self.beta
+
+  @alpha.setter
+  def alpha(self, alpha):
+    self.beta = 1.0 - float(alpha)
+
+  _reg_key = 'div'
+
+  def _reg_options(self) -> dict:
+    return dict(latent_reg='mmd', reg_coef=self.lamda - self.beta, mmd_kernel=self.mmd_kernel,
+                mmd_prior_samples=self.mmd_prior_samples, prior_seed=self.seed)
+
+  def _hyper_extra(self) -> dict:
+    return dict(reg_coef=self.lamda - self.beta)
+
+
+class DIPVAE(BetaVAE):
+  """dip_vae.py: a BetaVAE plus kl['dip_<latents>'] = disentangled_inferred_prior_loss(q(z|x), only_mean,
+  lambda_offdiag, lambda_diag) (losses.py:39-98), unscaled by beta; type I (only_mean) penalises Cov[E(z)], type II
+  E[Cov(z)] + Cov[E(z)].  Value and gradient: one launch per step (latent_reg.hip)."""
+
+  def __init__(self, only_mean: bool = False, lambda_diag: float = 1.0, lambda_offdiag: float = 2.0,
+               beta: float = 1.0, name='DIPVAE', **kwargs):
+    self.only_mean = bool(only_mean)
+    self.lambda_diag, self.lambda_offdiag = float(lambda_diag), float(lambda_offdiag)
+    super().__init__(beta=beta, name=name, **kwargs)
+
+  _reg_key = 'dip'
+
+  def _reg_options(self) -> dict:
+    return dict(latent_reg='dip_i' if self.only_mean else 'dip_ii', reg_coef=1.0,
+                dip_lambda=(self.lambda_diag, self.lambda_offdiag))
 
 
 # ======================================================================================
@@ -1544,7 +1615,7 @@ class FactorVAE(AnnealingVAE):
 def get_vae(name: str):
   """odin/bay/vi/autoencoder/__init__.py:28"""
   table = {c.__name__.lower(): c for c in (VariationalAutoencoder, BetaVAE, AnnealingVAE,
-                                           BetaTCVAE, FactorVAE, BetaCapacityVAE)}
+                                           BetaTCVAE, FactorVAE, BetaCapacityVAE, InfoVAE, DIPVAE)}
   table['vae'] = VariationalAutoencoder
   key = str(name).lower().replace('_', '')
   if key not in table:
