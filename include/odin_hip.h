@@ -321,6 +321,11 @@ int odin_disc_head_fwd_bwd(const float* h, const float* w, const float* bias, fl
 int odin_elbo_bernoulli_fwd_bwd(const float* logits, const float* x, float* llk_part,
                                 float* dlogits, const float* scale, int B, int n_per_sample,
                                 int* n_part_out, void* stream);
+/* The same, and dlogits_amax (optional) receives max |dlogits| -- the range word of the decoder's top gradient.  The
+ * a-priori bound 1 / B holds only for targets in [0, 1]; the reference's Bernoulli takes any real target. */
+int odin_elbo_bernoulli_fwd_bwd_ranged(const float* logits, const float* x, float* llk_part,
+                                       float* dlogits, const float* scale, int B, int n_per_sample,
+                                       int* n_part_out, uint32_t* dlogits_amax, void* stream);
 /* Independent(Normal(loc, scale)) with params = split(h,2,axis=-1)
  * (image_networks.py:95-102): softplus1 = 1 -> scale = softplus(raw + softplus^-1(1))
  * (GaussianLayer, odin/bay/layers/continuous.py:196-260; odin/backend/maths.py:279-281);

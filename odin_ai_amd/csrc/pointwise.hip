@@ -100,13 +100,14 @@ __global__ __launch_bounds__(256) void elbo_bernoulli_kernel(const float* __rest
                                                              float* __restrict__ llk_part,
                                                              float* __restrict__ dlogits,
                                                              const float* __restrict__ scale,
-                                                             int N, int n_part, int vec) {
+                                                             int N, int n_part, int vec,
+                                                             unsigned* __restrict__ g_amax) {
   __shared__ float red[4];
   const int b = blockIdx.x / n_part, part = blockIdx.x - b * n_part;
   const size_t base = (size_t)b * N;
   const int i0 = part * ELBO_CHUNK + threadIdx.x * 4;
   const float sc = scale[0];
-  float acc = 0.f;
+  float acc = 0.f, amx = 0.f;
   if (vec && i0 + 3 < N) {
     float4 l = *reinterpret_cast<const float4*>(logits + base + i0);
     float4 t = *reinterpret_cast<const float4*>(x + base + i0);
@@ -116,16 +117,20 @@ __global__ __launch_bounds__(256) void elbo_bernoulli_kernel(const float* __rest
     acc += t.z * l.z - softplus_f(l.z); g.z = (sigmoid_f(l.z) - t.z) * sc;
     acc += t.w * l.w - softplus_f(l.w); g.w = (sigmoid_f(l.w) - t.w) * sc;
     *reinterpret_cast<float4*>(dlogits + base + i0) = g;
+    amx = odin_amax3(odin_amax3(amx, g.x, g.y), g.z, g.w);
   } else {
     for (int j = 0; j < 4; ++j) {
       int i = i0 + j;
       if (i < N) {
         float l = logits[base + i], t = x[base + i];
         acc += t * l - softplus_f(l);
-        dlogits[base + i] = (sigmoid_f(l) - t) * sc;
+        const float g = (sigmoid_f(l) - t) * sc;
+        dlogits[base + i] = g;
+        amx = fmaxf(amx, fabsf(g));
       }
     }
   }
+  odin_amax_commit_wave(g_amax, amx, threadIdx.x & 63, blockIdx.x * 4 + (threadIdx.x >> 6));
   float s = block_sum_256(acc, red);
   if (threadIdx.x == 0) llk_part[blockIdx.x] = s;
 }
@@ -207,7 +212,7 @@ __device__ __forceinline__ void bern1(float l, float t, float sc, float& acc, fl
 template <int U>
 __global__ __launch_bounds__(256) void elbo_bernoulli_stream_kernel(
     const float4* __restrict__ logits, const float4* __restrict__ x, float* __restrict__ llk_part,
-    float4* __restrict__ dlogits, const float* __restrict__ scale, size_t n_waves) {
+    float4* __restrict__ dlogits, const float* __restrict__ scale, size_t n_waves, unsigned* __restrict__ g_amax) {
   const size_t w = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (w >= n_waves) return;
   const int lane = threadIdx.x & 63;
@@ -218,7 +223,7 @@ __global__ __launch_bounds__(256) void elbo_bernoulli_stream_kernel(
 #pragma unroll
   for (int u = 0; u < U; ++u) t[u] = x[base + 64 * u];
   const float sc = scale[0];
-  float acc = 0.f;
+  float acc = 0.f, amx = 0.f;
 #pragma unroll
   for (int u = 0; u < U; ++u) {
     float4 g;
@@ -226,6 +231,7 @@ __global__ __launch_bounds__(256) void elbo_bernoulli_stream_kernel(
     bern1(l[u].y, t[u].y, sc, acc, g.y);
     bern1(l[u].z, t[u].z, sc, acc, g.z);
     bern1(l[u].w, t[u].w, sc, acc, g.w);
+    amx = odin_amax3(odin_amax3(amx, g.x, g.y), g.z, g.w);
     // non-temporal store: measured on the same traffic (tools/elbo_ceiling.py, odin_debug_stream_probe) a 38 MB cold
     // stream reaches 4.4 TB/s with plain stores and 5.7 TB/s with streaming ones -- the written lines do not wait in
     // the caches behind the reads
@@ -233,6 +239,7 @@ __global__ __launch_bounds__(256) void elbo_bernoulli_stream_kernel(
   }
   acc = wave_sum64(acc);
   if (lane == 0) llk_part[w] = acc;
+  odin_amax_commit_wave(g_amax, amx, lane, (unsigned)w);
 }
 
 // The same as a persistent grid: 512 workgroups walk the 256-element chunks (64 lanes x float4; a chunk lies inside
@@ -242,10 +249,11 @@ __global__ __launch_bounds__(256) void elbo_bernoulli_stream_kernel(
 template <int U>
 __global__ __launch_bounds__(256) void elbo_bernoulli_gs_kernel(
     const float4* __restrict__ logits, const float4* __restrict__ x, float* __restrict__ llk_part,
-    float4* __restrict__ dlogits, const float* __restrict__ scale, size_t n_chunks) {
+    float4* __restrict__ dlogits, const float* __restrict__ scale, size_t n_chunks, unsigned* __restrict__ g_amax) {
   const size_t nw = (size_t)gridDim.x * 4;
   const int lane = threadIdx.x & 63;
   const float sc = scale[0];
+  float amx = 0.f;
   for (size_t c0 = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6); c0 < n_chunks; c0 += nw * U) {
     float4 l[U], t[U];
 #pragma unroll
@@ -266,12 +274,14 @@ __global__ __launch_bounds__(256) void elbo_bernoulli_gs_kernel(
         bern1(l[u].y, t[u].y, sc, acc, g.y);
         bern1(l[u].z, t[u].z, sc, acc, g.z);
         bern1(l[u].w, t[u].w, sc, acc, g.w);
+        amx = odin_amax3(odin_amax3(amx, g.x, g.y), g.z, g.w);
         odin_store4_stream(dlogits + c * 64 + lane, g);
         acc = odin_wave_sum64_valu(acc);
         if (lane == 0) llk_part[c] = acc;
       }
     }
   }
+  odin_amax_commit_wave(g_amax, amx, lane, blockIdx.x * 4 + (threadIdx.x >> 6));
 }
 
 // The same walk software-pipelined (round 6): the loads of the NEXT U chunks are issued before the current ones are
@@ -280,12 +290,13 @@ __global__ __launch_bounds__(256) void elbo_bernoulli_gs_kernel(
 template <int U>
 __global__ __launch_bounds__(256) void elbo_bernoulli_gsp_kernel(
     const float4* __restrict__ logits, const float4* __restrict__ x, float* __restrict__ llk_part,
-    float4* __restrict__ dlogits, const float* __restrict__ scale, size_t n_chunks) {
+    float4* __restrict__ dlogits, const float* __restrict__ scale, size_t n_chunks, unsigned* __restrict__ g_amax) {
   const size_t nw = (size_t)gridDim.x * 4;
   const int lane = threadIdx.x & 63;
   const float sc = scale[0];
   size_t c0 = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (c0 >= n_chunks) return;
+  float amx = 0.f;
   f32x4 l[U], t[U], ln[U], tn[U];
   const f32x4* lg = reinterpret_cast<const f32x4*>(logits);
   const f32x4* xg = reinterpret_cast<const f32x4*>(x);
@@ -314,6 +325,7 @@ __global__ __launch_bounds__(256) void elbo_bernoulli_gsp_kernel(
         bern1(l[u].y, t[u].y, sc, acc, g.y);
         bern1(l[u].z, t[u].z, sc, acc, g.z);
         bern1(l[u].w, t[u].w, sc, acc, g.w);
+        amx = odin_amax3(odin_amax3(amx, g.x, g.y), g.z, g.w);
         odin_store4_stream(dlogits + c * 64 + lane, g);
         acc = odin_wave_sum64_valu(acc);
         if (lane == 0) llk_part[c] = acc;
@@ -324,6 +336,7 @@ __global__ __launch_bounds__(256) void elbo_bernoulli_gsp_kernel(
     for (int u = 0; u < U; ++u) { l[u] = ln[u]; t[u] = tn[u]; }
     c0 = c1;
   }
+  odin_amax_commit_wave(g_amax, amx, lane, blockIdx.x * 4 + (threadIdx.x >> 6));
 }
 
 // h [B, n_pix, 2C] (loc | raw scale), x [B, n_pix, C]; N = n_pix*C elements per sample
@@ -958,6 +971,14 @@ extern "C" int odin_debug_elbo_shape(int blocks, int U, int pipelined) {
 extern "C" int odin_elbo_bernoulli_fwd_bwd(const float* logits, const float* x, float* llk_part,
                                            float* dlogits, const float* scale, int B,
                                            int n_per_sample, int* n_part_out, void* stream) {
+  return odin_elbo_bernoulli_fwd_bwd_ranged(logits, x, llk_part, dlogits, scale, B, n_per_sample, n_part_out, nullptr,
+                                            stream);
+}
+
+extern "C" int odin_elbo_bernoulli_fwd_bwd_ranged(const float* logits, const float* x, float* llk_part,
+                                                  float* dlogits, const float* scale, int B, int n_per_sample,
+                                                  int* n_part_out, uint32_t* dlogits_amax, void* stream) {
+  unsigned* g_amax = reinterpret_cast<unsigned*>(dlogits_amax);
   // large tensors: the persistent form (one partial per 256-element chunk)
   if (n_per_sample % 256 == 0 && (size_t)B * n_per_sample >= (1u << 20) && !ODIN_DIAG_ENV("ODIN_ELBO_U") &&
       (((uintptr_t)logits | (uintptr_t)x | (uintptr_t)dlogits) & 15) == 0) {
@@ -974,7 +995,7 @@ extern "C" int odin_elbo_bernoulli_fwd_bwd(const float* logits, const float* x, 
     if (g_elbo_gs[2]) {
 #define ODIN_ELBO_GSP_LAUNCH(UU)                                                                             \
   ODIN_LAUNCH((elbo_bernoulli_gsp_kernel<UU>), dim3(blocks), dim3(256), 0, stream, (const float4*)logits,   \
-              (const float4*)x, llk_part, (float4*)dlogits, scale, n_chunks)
+              (const float4*)x, llk_part, (float4*)dlogits, scale, n_chunks, g_amax)
       if (U == 1) ODIN_ELBO_GSP_LAUNCH(1);
       else if (U == 2) ODIN_ELBO_GSP_LAUNCH(2);
       else if (U == 3) ODIN_ELBO_GSP_LAUNCH(3);
@@ -984,7 +1005,7 @@ extern "C" int odin_elbo_bernoulli_fwd_bwd(const float* logits, const float* x, 
     }
 #define ODIN_ELBO_GS_LAUNCH(UU)                                                                              \
   ODIN_LAUNCH((elbo_bernoulli_gs_kernel<UU>), dim3(blocks), dim3(256), 0, stream, (const float4*)logits,    \
-              (const float4*)x, llk_part, (float4*)dlogits, scale, n_chunks)
+              (const float4*)x, llk_part, (float4*)dlogits, scale, n_chunks, g_amax)
     if (U == 2) ODIN_ELBO_GS_LAUNCH(2);
     else if (U == 3) ODIN_ELBO_GS_LAUNCH(3);
     else if (U == 6) ODIN_ELBO_GS_LAUNCH(6);
@@ -1002,7 +1023,7 @@ extern "C" int odin_elbo_bernoulli_fwd_bwd(const float* logits, const float* x, 
     const dim3 grid((unsigned)((n_waves + 3) / 4));
 #define ODIN_ELBO_STREAM(UU)                                                                    \
   ODIN_LAUNCH((elbo_bernoulli_stream_kernel<UU>), grid, dim3(256), 0, stream,                   \
-              (const float4*)logits, (const float4*)x, llk_part, (float4*)dlogits, scale, n_waves)
+              (const float4*)logits, (const float4*)x, llk_part, (float4*)dlogits, scale, n_waves, g_amax)
     if (U == 3) ODIN_ELBO_STREAM(3);
     else if (U == 4) ODIN_ELBO_STREAM(4);
     else if (U == 2) ODIN_ELBO_STREAM(2);
@@ -1015,7 +1036,7 @@ extern "C" int odin_elbo_bernoulli_fwd_bwd(const float* logits, const float* x, 
   if (logits == nullptr) return 0;
   int vec = (n_per_sample % 4 == 0) ? 1 : 0;
   ODIN_LAUNCH(elbo_bernoulli_kernel, dim3(B * n_part), dim3(256), 0, stream, logits, x, llk_part,
-              dlogits, scale, n_per_sample, n_part, vec);
+              dlogits, scale, n_per_sample, n_part, vec, g_amax);
   return odin_check_launch("elbo_bernoulli");
 }
 

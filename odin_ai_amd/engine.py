@@ -246,7 +246,7 @@ class NetProgram:
     the slab reduction that clears the words (NetProgram.backward alone does not clear them)."""
     n = len(self.recs) if upto is None else upto
     for i in range(first, n):   # (gouts below `first` stay inside a fused bottleneck launch: never written)
-      if self.dy_word[i] is None or self.dy_word[i] != self.word(i):   # (no word, or the caller's own static bound)
+      if self.dy_word[i] is None or self.dy_word[i] != self.word(i):   # (no word, or a word outside this buffer)
         continue
       blk = self.range_words[RANGE_WORDS * i:RANGE_WORDS * (i + 1)]
       bound = float(blk.view(torch.float32).max().item())
@@ -471,8 +471,8 @@ class VAEEngine:
       hyper_ring       per-step scalars from the device-resident ring; False: one 80-byte copy per step
       hyper_ring_rows  rows of that ring (a power of two >= 8)
       fuse_norm        the gradient norm's stage-1 sums ride in the slab reduction (odin_slab_reduce_sumsq)
-      static_top_word  the Bernoulli ELBO kernel's gradient travels with its a-priori bound 1 / B as a static range word; False:
-                       one absmax pass per step bounds it (A/B)
+      static_top_word  the Bernoulli ELBO kernel keeps the range word of its gradient itself (max |dlogits|, folded as
+                       it stores); False: one absmax pass per step bounds it (A/B)
       overlap_wgrad    None | 'small': the bottleneck layers' weight gradients on side streams (slower since round 2,
                        profiles/r05_ab_same_call.txt; kept for the multi-bucket DP step's tests)
       early_reduce     with overlap_wgrad: the decoder's slabs reduced on a side stream beside the encoder's backward
@@ -564,17 +564,13 @@ class VAEEngine:
                           use_act_words=act_words, small_wgrad_gf=small_wgrad_gf)
     self._act_words_dirty = False   # a forward pass has written activation words that no backward pass has cleared
     # The top gradient of a Bernoulli observation that is NOT produced by a fused tail comes from the stand-alone ELBO kernel
-    # (dlogits = (sigmoid(l) - x) / B_global): its bound is known a priori, |dlogits| <= 1 / B_global, so the last layer's
-    # plane kernels read a STATIC range word holding that bound instead of paying one absmax pass per step for it (the dense
-    # MNIST step: 5 of 125 us; a bound within a factor of two of the maximum costs at most one of the 22 bits).  The word is
-    # outside the buffer the step clears.
-    self._bern_word = None
-    if observation == 'bernoulli' and static_top_word:
-      self._bern_word = torch.zeros(RANGE_WORDS, dtype=torch.int32, device=self.device)
-      self._bern_word[:1] = torch.tensor([1.0 / (B * self.world_size)], dtype=torch.float32).view(torch.int32).to(self.device)
-      self.dec.dy_word[-1] = self._bern_word.data_ptr()
-      if self.dec.descs[-1] is not None:
-        self.dec.descs[-1].dy_amax = self._bern_word.data_ptr()
+    # (dlogits = (sigmoid(l) - x) / B_global), which folds max |dlogits| into the last layer's word as it stores the
+    # tensor: no absmax pass per step for it (the dense MNIST step: 5 of 125 us).  (Round 6 handed the consumers the
+    # a-priori bound 1 / B as a static word instead; that bound holds only for targets in [0, 1], and the reference's
+    # Bernoulli takes any real target: a target of 6 overflowed the planes to inf.)
+    self._bern_keeps_top = observation == 'bernoulli' and bool(static_top_word)
+    if self._bern_keeps_top:
+      self.dec.set_top_word(True)
     self.p = torch.empty(B, 2 * D, **f32)
     self.dp = torch.empty(B, 2 * D, **f32)
     self.eps = torch.zeros(B, D, **f32)
@@ -685,7 +681,7 @@ class VAEEngine:
     self.defer_wgrad = bool(defer_wgrad)
     self.graph = None
     # tests / debugging: verify every range word against its tensor before the slab reduction clears the words
-    # (synchronises; NetProgram.check_range_words)
+    # (synchronises; NetProgram.check_range_words); a callable is called as fn(engine) at that point instead
     self.debug_check_ranges = False
     self._jobs_keepalive = None
     self._jobs_cover_ok: Dict[tuple, bool] = {}
@@ -1306,9 +1302,9 @@ class VAEEngine:
     if self._used_fused or self._used_head:
       pass
     elif self.observation == 'bernoulli':
-      lib.odin_elbo_bernoulli_fwd_bwd(h_d.data_ptr(), x.data_ptr(), self.llk_part.data_ptr(),
-                                      gl.data_ptr(), self.hp(H_INVB), B, self.n_per,
-                                      C.byref(npart), st)
+      lib.odin_elbo_bernoulli_fwd_bwd_ranged(h_d.data_ptr(), x.data_ptr(), self.llk_part.data_ptr(),
+                                             gl.data_ptr(), self.hp(H_INVB), B, self.n_per, C.byref(npart),
+                                             self.dec.dy_word[-1] if self._bern_keeps_top else None, st)
     elif self.observation == 'mixqlogistic':
       Cc = self.in_shape[-1]
       lib.odin_elbo_mixqlogistic_fwd_bwd(h_d.data_ptr(), x.data_ptr(), self.llk_part.data_ptr(),
@@ -1594,8 +1590,12 @@ class VAEEngine:
     arr = (ReduceJob * len(jobs))(*jobs)
     self._jobs_keepalive = arr
     lib.odin_wgrad_planes_defer_end(st)   # (no-op unless backward() opened a collection)
-    if self.debug_check_ranges:
-      self.dec.check_range_words(first=self._dec_first() - 1 if self._bwd_neck() else 0)
+    if callable(self.debug_check_ranges):
+      self.debug_check_ranges(self)   # (a caller's audit of every word, on the same words: tests/range_audit.py)
+    elif self.debug_check_ranges:
+      # (a fused tail / head writes gouts[-2] itself: gouts[-1] is not produced in that step, its word stays zero)
+      self.dec.check_range_words(upto=len(self.dec_recs) - 1 if (self._used_fused or self._used_head) else None,
+                                 first=self._dec_first() - 1 if self._bwd_neck() else 0)
       self.enc.check_range_words()
     self._norm_parts = 0
     if getattr(self, '_fuse_norm_now', False) and not early:
