@@ -470,6 +470,22 @@ int odin_dip_moments(const float* p_local, float* block, int B_local, int D, voi
 int odin_dip_finish(const float* blocks, int world, const float* p_local, float* ws, float* dloc,
                     float* dscale, const float* coef, const float* coef_grad, int B_local, int D, int type2,
                     float lambda_diag, float lambda_offdiag, void* stream);
+/* ---- VampriorVAE's prior (odin/bay/vi/autoencoder/vamprior.py:25-107): the uniform mixture of the K posteriors
+ * q(z | u_k) = N(loc_k, softplus(raw_k)), pu [K, 2D] = (loc | raw), as a correction to the standard-normal KL:
+ *   c[b] = log N(z_b; 0, I) - ( logsumexp_k sum_d log N(z_bd; loc_kd, sigma_kd) - log K )      (kl_vamp = kl_std + c)
+ * ws[0] = coef[0] * mean_b c[b]; dz [B, D] = coef_grad[0] * d(sum_b c_b)/dz, dpu [K, 2D] = coef_grad[0] *
+ * d(sum_b c_b)/d(loc | raw) (through softplus); coef / coef_grad: DEVICE scalars or NULL (1); dz and dpu both NULL:
+ * forward only (the same c and ws[0] bit for bit).  Three launches inside the call (component table | rows | components);
+ * the row maximum is subtracted, sums over k and over b run in float64 in a fixed order inside one workgroup each: no
+ * atomics, bit-reproducible; no [B, K] tensor reaches memory beyond lse[B].  B <= 4096, K <= 1024, D <= 64, any values
+ * inside.  ws: odin_vamprior_workspace(B, K, D) floats, 8-byte aligned, no initialisation needed. */
+int odin_vamprior_workspace(int B, int K, int D);
+int odin_vamprior_fwd_bwd(const float* z, const float* pu, float* ws, float* c, float* dz, float* dpu,
+                          const float* coef, const float* coef_grad, int B, int K, int D, void* stream);
+/* u = clip(w, lo, hi) and clip_by_value's gradient in place, g = scale * g * [lo < w < hi] (the pseudo-inputs'
+ * hard_probs; scale: a constant factor of the chain between u and the tensor g was taken for, e.g. 2 for CenterAt0) */
+int odin_clip_range_fwd(const float* w, float* u, size_t n, float lo, float hi, void* stream);
+int odin_clip_range_bwd(const float* w, float* g, size_t n, float lo, float hi, float scale, void* stream);
 /* permute_dims (odin/bay/vi/utils.py:233-269): out[i,l] = z[perm[i,l], l]; perm int32 [B,D] */
 int odin_permute_dims(const float* z, const int32_t* perm, float* out, int B, int D, void* stream);
 /* per-column random permutations generated on device (Philox), perm int32 [B,D] */

@@ -464,7 +464,9 @@ class VAEEngine:
                side_streams: int = 2, small_wgrad_gf: float = 0.8, dp_buckets: Optional[int] = None,
                neck: bool = True, neck_bwd: Optional[bool] = None, static_top_word: bool = True,
                latent_reg: Optional[str] = None, reg_coef: float = 1.0, mmd_kernel: str = 'gaussian',
-               mmd_prior_samples: int = 100, dip_lambda: Tuple[float, float] = (1.0, 2.0), prior_seed: int = 0):
+               mmd_prior_samples: int = 100, dip_lambda: Tuple[float, float] = (1.0, 2.0), prior_seed: int = 0,
+               vamprior_components: Optional[int] = None, pseudoinputs_mean: float = -0.05,
+               pseudoinputs_std: float = 0.01, pseudoinputs=None):
     """The keyword-only arguments are the engine's launch-order / A-B options (tests and tools pass them; the engine
     reads no environment variable):
       act_words        activation range words for the two-plane consumers; False: unscaled planes
@@ -492,7 +494,15 @@ class VAEEngine:
       mmd_kernel         'gaussian' | 'linear'
       mmd_prior_samples  M prior samples per step, drawn on the device from (prior_seed, step)
       dip_lambda         (lambda_diag, lambda_offdiag)
-      prior_seed         key of the prior sample's stream: must be the same on every rank (unlike `seed`)"""
+      prior_seed         key of the prior sample's stream: must be the same on every rank (unlike `seed`)
+    The learned prior of VampriorVAE (vamprior.hip; excludes tc, latent_reg, analytic / forward KL, free
+    bits, capacity and data parallelism):
+      vamprior_components  None | K: the prior is the uniform mixture of q(z | u_k) at K trainable pseudo-inputs
+                           u = clip(W_u, 1e-6, 1 - 1e-6); W_u [K, prod(in_shape)] is the LAST entry of the parameter
+                           layout (key ('vamp', 'u')); the term beta * mean(c), c = log N(z; 0, I) - log p(z), is added to
+                           the loss and reported as out4[3]; `kl` stays the standard-normal KL, `vamp_c` holds c [B]
+      pseudoinputs_mean / pseudoinputs_std   W_u ~ Normal(mean, std) when the engine allocates its own parameters
+      pseudoinputs         an explicit [K, prod(in_shape)] array instead"""
     self.lib = lib if lib is not None else _lib.load()
     self.device = torch.device(device)
     self.B, self.D = int(batch_size), int(zdim)
@@ -519,6 +529,9 @@ class VAEEngine:
       raise NotImplementedError(f'mmd_kernel={mmd_kernel!r}: the HIP path offers {sorted(MMD_KERNELS)}')
     self.reg_mode, self.reg_coef = latent_reg, float(reg_coef)
     self.reg_sharded = latent_reg is not None and self.is_dp
+    self.vamp_K = None if vamprior_components is None else int(vamprior_components)
+    if self.vamp_K is not None:
+      self._check_vamprior(analytic, reverse, free_bits, tc, latent_reg, capacity, range_words)
     f32 = dict(dtype=torch.float32, device=self.device)
     # ---- parameters ----
     self.layout = ParamLayout()
@@ -528,13 +541,20 @@ class VAEEngine:
     self.lat_w_off = self.layout.add(('lat', 'w'), (self.hdim, 2 * self.D))
     self.lat_b_off = self.layout.add(('lat', 'b'), (2 * self.D,))
     self.dec_recs, do = build_layers('dec', dec_layers, (self.D,), self.layout)
+    if self.vamp_K is not None:
+      # the pseudo-inputs: one more parameter tensor behind the networks', so that gradients, Adam moments, the norm,
+      # the NaN guard and the checkpoint code see it like any other
+      self.vamp_u_off = self.layout.add(('vamp', 'u'), (self.vamp_K, int(np.prod(self.in_shape))))
     self.layout.pad_to(4)
     self.out_shape = do
     C_in = self.in_shape[-1]
     assert tuple(do) == self.in_shape[:-1] + (observation_maps(observation, C_in),), (do, self.in_shape)
     n = self.layout.size
+    own_params = params is None
     self.params = params if params is not None else torch.zeros(n, **f32)
     assert self.params.numel() == n
+    if self.vamp_K is not None and (own_params or pseudoinputs is not None):
+      self._init_pseudoinputs(pseudoinputs, pseudoinputs_mean, pseudoinputs_std)
     self.grads = torch.zeros(n, **f32)
     if optim_state is not None:
       self.m, self.v = optim_state
@@ -552,10 +572,13 @@ class VAEEngine:
     # forward and backward passes (FactorVAE's second half batch) folds its maxima into the same words -- still upper
     # bounds -- and needs no clearing launch of its own
     self._shared_ranges = range_words is not None
+    # (VampPrior: the pseudo-input pass's gradient | activation words behind the data pass's, in the same buffer -- the
+    # step's last backward launch clears them all)
+    npw = 2 * ne if self.vamp_K is not None else 0
     self.range_words = (range_words if range_words is not None else
-                        torch.zeros(2 * nl * RANGE_WORDS, dtype=torch.int32, device=self.device))
-    assert self.range_words.numel() == 2 * nl * RANGE_WORDS
-    gw, aw = self.range_words[:nl * RANGE_WORDS], self.range_words[nl * RANGE_WORDS:]
+                        torch.zeros((2 * nl + npw) * RANGE_WORDS, dtype=torch.int32, device=self.device))
+    assert self.range_words.numel() == (2 * nl + npw) * RANGE_WORDS
+    gw, aw = self.range_words[:nl * RANGE_WORDS], self.range_words[nl * RANGE_WORDS:2 * nl * RANGE_WORDS]
     self.enc = NetProgram(self.lib, self.enc_recs, B, self.device, self.params, self.grads, mr,
                           range_words=gw[:ne * RANGE_WORDS], act_words=aw[:ne * RANGE_WORDS],
                           use_act_words=act_words, small_wgrad_gf=small_wgrad_gf)
@@ -627,6 +650,8 @@ class VAEEngine:
     self._plan_latent_block(f32)
     self._neck_bwd_opt = neck_bwd
     self._plan_neck(f32, bool(neck))
+    if self.vamp_K is not None:
+      self._plan_vamprior(f32, mr, act_words, small_wgrad_gf)
     self.ws = torch.empty(4096, **f32)
     self.gnorm2 = torch.zeros(1, **f32)
     self.flag = torch.zeros(1, dtype=torch.int32, device=self.device)
@@ -717,6 +742,169 @@ class VAEEngine:
       self.dip_block_local = self.reg_ws[4:4 + bs]
       self.dip_blocks = self.reg_ws[4 + bs:4 + bs + W * bs]
     self._prior_explicit = False
+
+  # ---- VampPrior (vamprior.py:25-107) --------------------------------------------------------------------
+  VAMP_CLIP = (1e-6, 1.0 - 1e-6)   # hard_probs: clip_by_value(W_u, 1e-6, 1 - 1e-6)
+
+  def _check_vamprior(self, analytic, reverse, free_bits, tc, latent_reg, capacity, range_words):
+    K = self.vamp_K
+    if not 1 <= K <= 1024:
+      raise ValueError(f'vamprior_components={K}: the mixture kernel takes 1 .. 1024 components')
+    if not 1 <= self.B <= 4096 or not 1 <= self.D <= 64:
+      raise ValueError(f'vamprior_components: batch_size={self.B}, zdim={self.D} outside the kernel (4096, 64)')
+    if tc is not None:
+      raise ValueError(f'vamprior_components cannot be combined with tc={tc!r} (the same step scalars)')
+    if latent_reg is not None:
+      raise ValueError(f'vamprior_components cannot be combined with latent_reg={latent_reg!r} (the same step scalars)')
+    # (reverse=False without analytic=True never gets here: set_kl_form has raised TypeError)
+    if not reverse:
+      raise NotImplementedError('vamprior_components with reverse=False: KL(p || q) needs samples of the mixture')
+    if analytic:
+      raise NotImplementedError('vamprior_components with analytic=True: the KL to a mixture has no closed form')
+    if free_bits is not None:
+      raise NotImplementedError('vamprior_components with free_bits: the clamp acts on the standard-normal KL only')
+    if capacity:
+      raise NotImplementedError('vamprior_components with capacity=True (BetaCapacityVAE) is not offered')
+    if self.is_dp:
+      raise NotImplementedError('vamprior_components under data parallelism (world_size > 1 / force_dp) is not offered')
+    if range_words is not None:
+      raise NotImplementedError('vamprior_components with shared range_words is not offered')
+
+  def _init_pseudoinputs(self, pseudoinputs, mean, std):
+    K, n = self.vamp_K, int(np.prod(self.in_shape))
+    dst = self.params[self.vamp_u_off:self.vamp_u_off + K * n]
+    if pseudoinputs is not None:
+      a = torch.as_tensor(np.asarray(pseudoinputs, dtype=np.float32)).reshape(-1)
+      if a.numel() != K * n:
+        raise ValueError(f'pseudoinputs: expected [{K}, {n}], got {tuple(np.shape(pseudoinputs))}')
+      dst.copy_(a.to(self.device))
+      return
+    g = torch.Generator(device='cpu').manual_seed(self.seed + 0x76616D70)
+    dst.copy_((torch.randn(K * n, generator=g) * float(std) + float(mean)).to(self.device))
+
+  def _plan_vamprior(self, f32, max_rows, act_words, small_wgrad_gf):
+    """The pseudo-input pass: a second encoder program of batch K over the SAME parameters.  Its weight-gradient slab
+    rows are summed with the data pass's by the one reduction job per tensor: every encoder slab (and the three forms
+    of the projection's slab) is allocated tall enough for both, the data pass's rows first."""
+    K, D, ne = self.vamp_K, self.D, len(self.enc_recs)
+    if any(r.kind == 'deconv' for r in self.enc_recs):
+      raise NotImplementedError('vamprior_components: an encoder with Conv2DTranspose layers is not offered')
+    nl = ne + len(self.dec_recs)
+    pw = self.range_words[2 * nl * RANGE_WORDS:]
+    self.penc = NetProgram(self.lib, self.enc_recs, K, self.device, self.params, self.grads, max_rows,
+                           range_words=pw[:ne * RANGE_WORDS], act_words=pw[ne * RANGE_WORDS:],
+                           use_act_words=act_words, small_wgrad_gf=small_wgrad_gf)
+    self._penc_words_dirty = False
+    self._enc_tall: List[torch.Tensor] = []
+    for i in range(ne):
+      n = self.enc.wslabs[i].shape[1]
+      tall = torch.empty(self.enc.wrows[i] + self.penc.wrows[i], n, **f32)
+      self._enc_tall.append(tall)
+      self.enc.wslabs[i] = tall[:self.enc.wrows[i]]
+      self.penc.wslabs[i] = tall[self.enc.wrows[i]:]   # (re-pointed behind the rows the data pass wrote: _backward_pseudo)
+    rows = C.c_int(0)
+    self.lib.odin_dense_wgrad(None, None, None, C.byref(rows), K, self.hdim, 2 * D, None)
+    self.plat_rows = rows.value
+    # the projection's slab, whichever latent form runs
+    self.lat_slab = torch.empty(self.lat_rows + rows.value, self.lat_slab.shape[1], **f32)
+    if self.lat_block:
+      self.lb_slabl = torch.empty(self.lb_rows + rows.value, self.lb_slabl.shape[1], **f32)
+    if self.neck:
+      self.nk_slabl = torch.empty(self.nk_rows + rows.value, self.nk_slabl.shape[1], **f32)
+    n_u = K * self.n_per
+    self.vamp_u = torch.empty((K,) + self.in_shape, **f32)      # clip(W_u)
+    self.vamp_du = torch.empty(1, n_u, **f32)                     # d loss / d u, then masked: a one-row slab of dW_u
+    self.vamp_pu = torch.empty(K, 2 * D, **f32)                   # (loc | raw) of the K components
+    self.vamp_dpu = torch.empty(K, 2 * D, **f32)
+    self.vamp_c = torch.empty(self.B, **f32)
+    self.vamp_dz = torch.empty(self.B, D, **f32)
+    self.vamp_ws = torch.zeros(self.lib.odin_vamprior_workspace(self.B, K, D), **f32)
+
+  def pseudo_forward(self, st=None):
+    """u = clip(W_u) -> encoder -> projection: vamp_pu [K, 2D], the components of the prior (no sampling, no decoder)"""
+    lib, K, D = self.lib, self.vamp_K, self.D
+    st = self.stream() if st is None else st
+    lo, hi = self.VAMP_CLIP
+    lib.odin_clip_range_fwd(self.params[self.vamp_u_off:].data_ptr(), self.vamp_u.data_ptr(), self.vamp_u.numel(),
+                            lo, hi, st)
+    if self._penc_words_dirty:   # (a pseudo pass behind another one without a backward pass between them)
+      ne = len(self.enc_recs)
+      lib.odin_range_reset(self.penc.act_words.data_ptr(), ne, st)
+    self._penc_words_dirty = True
+    h = self.penc.forward(self.vamp_u, st)
+    lib.odin_dense_fwd(h.data_ptr(), self.params[self.lat_w_off:].data_ptr(), self.params[self.lat_b_off:].data_ptr(),
+                       self.vamp_pu.data_ptr(), K, self.hdim, 2 * D, 0, st)
+    return self.vamp_pu
+
+  def vamprior_log_prob(self, z: torch.Tensor, out: torch.Tensor, st=None):
+    """out[i] = log p_vamp(z_i) for ANY number of rows z [N, D] against the components pseudo_forward() left: the
+    forward-only launch over chunks of at most 4096 rows (a workspace of its own: the step's stays untouched)"""
+    st = self.stream() if st is None else st
+    N, D, K = z.shape[0], self.D, self.vamp_K
+    assert z.shape == (N, D) and z.is_contiguous() and out.is_contiguous() and out.numel() == N
+    step = min(N, 4096)
+    ws = torch.zeros(self.lib.odin_vamprior_workspace(step, K, D), dtype=torch.float32, device=self.device)
+    for i0 in range(0, N, step):
+      n = min(step, N - i0)
+      self.lib.odin_vamprior_fwd_bwd(z[i0:].data_ptr(), self.vamp_pu.data_ptr(), ws.data_ptr(), out[i0:].data_ptr(),
+                                     None, None, None, None, n, K, D, st)
+    # the launch leaves c = log N(z; 0, I) - log p(z)
+    out.copy_(-0.5 * (z * z).sum(1) - 0.5 * D * math.log(2.0 * math.pi) - out)
+    return out
+
+  def _backward_pseudo(self, st, jobs, late_jobs):
+    """dpu -> projection -> encoder at batch K -> du -> dW_u.  Every weight-gradient slab row this pass writes lands
+    right behind the rows the data pass wrote into the same slab, and the data pass's reduction job is extended over
+    them: one job per tensor sums both passes in a fixed order (odin_slab_reduce overwrites its destination)."""
+    lib, K, D, ne = self.lib, self.vamp_K, self.D, len(self.enc_recs)
+    g0 = self.grads.data_ptr()
+    by_dst = {jb.dst: jb for jb in list(jobs) + list(late_jobs)}
+
+    # Invariant: the data pass has left ONE slab reduction job per encoder tensor (and one for the projection) in
+    # `jobs` or `late_jobs`, its slab being the tall one planned in _plan_vamprior.  The engine builds its encoder
+    # program without direct_wgrad and never reduces encoder slabs early, so this holds for every option it offers; a
+    # new path that writes an encoder gradient without a slab job would stop at the assert below.
+    def data_job(off):
+      jb = by_dst.get(g0 + 4 * off)
+      assert jb is not None, f'no data-pass reduction job for the parameter at offset {off}'
+      return jb
+    h = self.penc.outs[-1]
+    last = self.enc_recs[-1]
+    # the projection: weight gradient (dWl | dbl) behind the data pass's rows, then the data gradient
+    jb = data_job(self.lat_w_off)
+    slab = next(t for t in (self.lat_slab, getattr(self, 'lb_slabl', None), getattr(self, 'nk_slabl', None))
+                if t is not None and t.data_ptr() == jb.src)
+    assert jb.rows + self.plat_rows <= slab.shape[0] and jb.stride == slab.shape[1] and jb.n == slab.shape[1]
+    rows = C.c_int(0)
+    lib.odin_dense_wgrad(h.data_ptr(), self.vamp_dpu.data_ptr(), slab[jb.rows:].data_ptr(), C.byref(rows), K, self.hdim,
+                         2 * D, st)
+    assert 0 < rows.value <= self.plat_rows
+    jb.rows += rows.value
+    aux_act = ACT[last.act]
+    # (dpu is read by fp32 kernels on this path: no range word for it; the projection's data gradient keeps the word
+    # of the pseudo encoder's top gradient)
+    top = self.penc.set_top_word(True)
+    lib.odin_dense_bwd(None, self.vamp_dpu.data_ptr(), self.params[self.lat_w_off:].data_ptr(),
+                       h.data_ptr() if aux_act != 0 else None, aux_act, self.penc.gouts[-1].data_ptr(), None,
+                       C.byref(rows), None, None, K, self.hdim, 2 * D, 0, 1, None, top, st)
+    for i, r in enumerate(self.enc_recs):
+      jb = data_job(r.w_off)
+      tall = self._enc_tall[i]
+      assert jb.src == tall.data_ptr() and jb.rows + self.penc.wrows[i] <= tall.shape[0]
+      self.penc.wslabs[i] = tall[jb.rows:]
+    pjobs = self.penc.backward(self.vamp_u, self.penc.gouts[-1], st, dx_out=self.vamp_du)
+    for pj in pjobs:
+      jb = by_dst[pj.dst]
+      assert pj.src == jb.src + 4 * jb.rows * jb.stride and pj.n == jb.n and pj.stride == jb.stride
+      jb.rows += pj.rows
+    # dW_u = du * [1e-6 < W_u < 1 - 1e-6], one complete slab row.  (The library's input gradient of a layer that
+    # centres its input, 2 x - 1, is taken with respect to the centred tensor: the factor 2 joins here.)
+    lo, hi = self.VAMP_CLIP
+    n_u = self.vamp_du.numel()
+    lib.odin_clip_range_bwd(self.params[self.vamp_u_off:].data_ptr(), self.vamp_du.data_ptr(), n_u, lo, hi,
+                            2.0 if self.enc_recs[0].center else 1.0, st)
+    jobs.append(ReduceJob(self.vamp_du.data_ptr(), g0 + 4 * self.vamp_u_off, n_u, 1, n_u, 0))
+    self._penc_words_dirty = False   # (cleared with the engine's words by the reduction that follows)
 
   def _comm(self):
     if self.comm is None:
@@ -1024,6 +1212,10 @@ class VAEEngine:
       # InfoVAE / DIPVAE: the term reg_coef * value; every rank back-propagates the full d(value)/d(its own rows), as
       # for beta-TC
       h[H_TCCOEF] = h[H_TCGRAD] = self.reg_coef if reg_coef is None else float(reg_coef)
+    if self.vamp_K is not None:
+      # VampPrior: the term beta * mean_b c_b; its gradient beta / B_global * d(sum_b c_b)
+      h[H_TCCOEF] = beta
+      h[H_TCGRAD] = beta / Bg
     if extra is not None:  # second optimiser's Adam block (FactorVAE discriminator), slots 10..14
       for i, val in enumerate(extra):
         h[10 + i] = float(val)
@@ -1205,6 +1397,8 @@ class VAEEngine:
     lb = self.params[self.lat_b_off:]
     self._used_block = self.lat_block and fused
     self._used_neck = self.neck and fused
+    if self.vamp_K is not None:
+      self.pseudo_forward(st)   # the prior's components: independent of the data batch
     self._clear_stale_act_words(st)
     # (outs[0] of the decoder comes from the bottleneck launch in the fused step: no word for layer 1's input then)
     if len(self.dec_recs) > 1:
@@ -1358,6 +1552,12 @@ class VAEEngine:
                            self.reg_dscale.data_ptr() if self.dip_type2 else None, None, self.hp(H_TCGRAD), B, D,
                            self.dip_type2, self.dip_lambda[0], self.dip_lambda[1], st)
       tcp = self.reg_ws.data_ptr()
+    elif self.vamp_K is not None:
+      # (the value unscaled: the finalisation multiplies it by H_TCCOEF = beta, once)
+      lib.odin_vamprior_fwd_bwd(self.z.data_ptr(), self.vamp_pu.data_ptr(), self.vamp_ws.data_ptr(),
+                                self.vamp_c.data_ptr(), self.vamp_dz.data_ptr(), self.vamp_dpu.data_ptr(), None,
+                                self.hp(H_TCGRAD), B, self.vamp_K, D, st)
+      tcp = self.vamp_ws.data_ptr()
     self._llk_part_used = llk_part
     if tc_ptr is not None:
       tcp = tc_ptr
@@ -1537,6 +1737,9 @@ class VAEEngine:
     elif self.reg_mode is not None:
       tl = self.reg_dloc.data_ptr()
       ts = self.reg_dscale.data_ptr() if self.dip_type2 else None
+    if self.vamp_K is not None:
+      assert extra_dz is None
+      dzx = self.vamp_dz.data_ptr()
     h_e = self.enc.outs[-1]
     last = self.enc_recs[-1]
     aux_act = ACT[last.act]
@@ -1579,6 +1782,8 @@ class VAEEngine:
                               rows.value, last.b_n, 0))
     if not self._bwd_neck():
       jobs += self.enc.backward(self.x, self.enc.gouts[-1], st, fork=fork)
+    if self.vamp_K is not None:
+      self._backward_pseudo(st, jobs, late_jobs)
     jobs += late_jobs
     # the range words of the gradient tensors (their producers fold in with atomicMax, so every step starts from
     # zero): cleared by the step's LAST backward launch -- a reduction over zero slab rows writes zeros -- instead
@@ -1758,7 +1963,8 @@ class VAEEngine:
       def fwd():
         self.forward(x, eps, finalize=False, prior=prior)
         tcp = (self.tc_ws.data_ptr() if self.tc_mode == 'betatc' else
-               self.reg_ws.data_ptr() if self.reg_mode is not None else None)
+               self.reg_ws.data_ptr() if self.reg_mode is not None else
+               self.vamp_ws.data_ptr() if self.vamp_K is not None else None)
         self._fin_pending = (self._llk_part_used.data_ptr(), self.n_part, tcp)
       P.append(('k', fwd))
     if self.is_dp and self.dp_buckets >= 2:

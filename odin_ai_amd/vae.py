@@ -410,6 +410,8 @@ class VariationalAutoencoder:
     deconv = {r.key for r in eng.enc_recs + eng.dec_recs if r.kind == 'deconv'}
     for key, shp, off in eng.layout.entries:
       n = int(np.prod(shp))
+      if key[0] == 'vamp':   # (the pseudo-inputs: drawn by the engine, VAEEngine._init_pseudoinputs)
+        continue
       if key[-1] == 'b':
         eng.params[off:off + n].zero_()
         continue
@@ -479,6 +481,13 @@ class VariationalAutoencoder:
   def _hyper_extra(self) -> dict:
     """per-step scalars beyond (lr, beta) that a subclass hands to the engine (BetaCapacityVAE: the capacity)"""
     return {}
+
+  def _prior_log_prob(self, eng: VAEEngine, z: torch.Tensor, lp: torch.Tensor):
+    """marginal_log_prob: lp [n, B] holds log N(z; 0, I) of the samples z [n, B, D]; a model with another prior
+    overwrites it (VampriorVAE)"""
+
+  def _step_metrics(self, out: torch.Tensor, metrics: Dict[str, torch.Tensor]):
+    """optimize: a subclass's view of the step scalars out = [loss, mean llk, mean beta * kl, extra term]"""
 
   # the batch regulariser of InfoVAE / DIPVAE: engine options and the key of its term in `kl` / the metrics
   _reg_key: Optional[str] = None
@@ -600,6 +609,7 @@ class VariationalAutoencoder:
       lq, lp, llk = torch.empty(n, B, **f32), torch.empty(n, B, **f32), torch.empty(n, B, **f32)
       lib.odin_latent_sample_logprob(eng.p.data_ptr(), e.data_ptr(), z.data_ptr(), lq.data_ptr(),
                                      lp.data_ptr(), n, B, D, st)
+      self._prior_log_prob(eng, z, lp)
       # decode the n*B codes in chunks of whole sample-rows (bounded activation memory)
       rows = max(1, min(n, 2048 // max(B, 1)))
       for k0 in range(0, n, rows):
@@ -671,6 +681,7 @@ class VariationalAutoencoder:
       metrics[f'tc_{self.latents.name}'] = out[3]
     if self._reg_key is not None:
       metrics[f'{self._reg_key}_{self.latents.name}'] = out[3]
+    self._step_metrics(out, metrics)
     if training and track_gradients:
       for k, g in eng.grad_views().items():
         metrics['_grad/' + self.variable_name(k)] = g.clone()
@@ -690,6 +701,8 @@ class VariationalAutoencoder:
     """Keras variable name of a parameter key: the reference's layer names
     (image_networks.py:248-268,463-511: encoder0.., encoder_proj, decoder_proj, decoder1..;
     DistributionDense 'latents', dense_distribution.py:229-238) + /kernel | /bias."""
+    if key[0] == 'vamp':
+      return VAMPRIOR_VARIABLE
     suffix = 'kernel' if key[-1] == 'w' else 'bias'
     if key[0] == 'lat':
       return f'{self.latents.name}/{suffix}'
@@ -1064,6 +1077,122 @@ class DIPVAE(BetaVAE):
   def _reg_options(self) -> dict:
     return dict(latent_reg='dip_i' if self.only_mean else 'dip_ii', reg_coef=1.0,
                 dip_lambda=(self.lambda_diag, self.lambda_offdiag))
+
+
+# checkpoint name of the pseudo-input variable W_u [n_components, prod(input_shape)]: the kernel of the bias-free Dense
+# layer `Vamprior.means` (vamprior.py:74-82).  Like the other names of the 'tf' format it has never been opened by
+# TensorFlow itself.
+VAMPRIOR_VARIABLE = 'vamprior/means/kernel'
+
+
+class Vamprior:
+  """vamprior.py:25-133: p(z) = 1/K sum_k q(z | u_k), the encoder's own posteriors at the K learned pseudo-inputs
+  u = clip(W_u, 1e-6, 1 - 1e-6).  The components are recomputed from the model's current weights at every call."""
+
+  def __init__(self, vae: 'VampriorVAE'):
+    self._vae = vae
+    self.n_components = int(vae.n_components)
+    self.input_shape = tuple(vae.input_shape)
+
+  def _eng(self) -> VAEEngine:
+    """the model's batch-1 engine (always there: build() made it) with the components of the current weights"""
+    eng = self._vae._engine(1)
+    eng.pseudo_forward()
+    return eng
+
+  @property
+  def pseudoinputs(self) -> torch.Tensor:
+    """the clipped pseudo-inputs [K, *input_shape]"""
+    return self._eng().vamp_u.clone()
+
+  @property
+  def distribution(self) -> MVNDiagPosterior:
+    """q(z | u_k), k = 0 .. K - 1 (its cached sample: the means); ONE pass of the encoder at batch K -- take
+    mean() / stddev() of the returned object when both are wanted"""
+    eng = self._eng()
+    p = eng.vamp_pu.clone()
+    return MVNDiagPosterior(p, p[:, :eng.D].clone(), eng.D)
+
+  def mean(self):
+    return self.distribution.mean()
+
+  def stddev(self):
+    return self.distribution.stddev()
+
+  def log_prob(self, z) -> torch.Tensor:
+    """log p(z) [n] for z [n, D], any n: the mixture kernel, forward only (vamprior.hip), through the one engine"""
+    z = _as_tensor(z, self._vae.device).reshape(-1, self._vae.zdim).contiguous()
+    return self._eng().vamprior_log_prob(z, torch.empty(z.shape[0], dtype=torch.float32, device=z.device))
+
+  def sample(self, n: int = 1, seed: Optional[int] = None) -> torch.Tensor:
+    """_sample_n (vamprior.py:121-131): n DISTINCT components by a seeded shuffle, one posterior sample of each.
+    (TensorFlow's random stream is not reproduced: the draw is a function of `seed` through torch's generator.)"""
+    n = int(n)
+    if not 1 <= n <= self.n_components:
+      raise ValueError(f'Vamprior.sample: n={n} outside [1, n_components={self.n_components}] (distinct components)')
+    g = torch.Generator(device='cpu')
+    if seed is not None:
+      g.manual_seed(int(seed))
+    ids = torch.randperm(self.n_components, generator=g)[:n]
+    q = self.distribution
+    e = torch.randn(n, q.loc.shape[1], generator=g).to(q.loc.device)
+    ids = ids.to(q.loc.device)
+    return (q.loc[ids] + q.scale[ids] * e).contiguous()
+
+
+class VampriorVAE(BetaVAE):
+  """vamprior.py:136-170 (Tomczak & Welling 2018): a BetaVAE whose latent prior is the Vamprior.  The Monte-Carlo KL of
+  the step is log q(z|x) - log p_vamp(z): the fused kernels keep computing the standard-normal KL and the mixture
+  kernel adds the correction c = log N(z; 0, I) - log p_vamp(z) (vamprior.hip), so
+  kl['kl_<latents>'] = beta * (kl_std + c).  `pseudoinputs`: an explicit [n_components, prod(input_shape)] array for
+  W_u (the reference's Vamprior takes it; its VampriorVAE does not pass it on).  Not offered with this prior:
+  analytic / forward KL, free_bits, sample_shape other than (), data parallelism."""
+
+  def __init__(self, n_components: int = 500, pseudoinputs_mean: float = -0.05, pseudoinputs_std: float = 0.01,
+               beta: Union[float, Interpolation] = linear(vmin=1e-6, vmax=1., steps=2000, delay_in=0),
+               pseudoinputs=None, name='VampriorVAE', **kwargs):
+    self.n_components = int(n_components)
+    self.pseudoinputs_mean, self.pseudoinputs_std = float(pseudoinputs_mean), float(pseudoinputs_std)
+    self._pseudoinputs = pseudoinputs
+    ss = kwargs.get('sample_shape', ())
+    if isinstance(ss, int) or tuple(ss) != ():
+      raise NotImplementedError(f'VampriorVAE with sample_shape={ss!r}: one sample of z per input only')
+    self.vamprior: Optional[Vamprior] = None
+    super().__init__(beta=beta, name=name, **kwargs)
+
+  def build(self, input_shape):
+    ret = super().build(input_shape)
+    self.vamprior = Vamprior(self)
+    self.latents.prior = self.vamprior
+    return ret
+
+  def _reg_options(self) -> dict:
+    # (an explicit array initialises W_u once: later engines share the parameter buffer)
+    return dict(vamprior_components=self.n_components, pseudoinputs_mean=self.pseudoinputs_mean,
+                pseudoinputs_std=self.pseudoinputs_std,
+                pseudoinputs=self._pseudoinputs if self._params is None else None)
+
+  def set_elbo_configs(self, analytic=None, reverse=None, free_bits=None, sample_shape=None):
+    if analytic or reverse is False or free_bits is not None or sample_shape not in (None, ()):
+      raise NotImplementedError('VampriorVAE: analytic / forward KL, free_bits and sample_shape are not offered')
+    return super().set_elbo_configs(analytic, reverse, free_bits, sample_shape)
+
+  def elbo_components(self, inputs, training=None, mask=None, eps=None, **kwargs):
+    llk, kl = super().elbo_components(inputs, training=training, mask=mask, eps=eps, **kwargs)
+    eng = self._engine(_as_tensor(inputs, self.device).shape[0])
+    key = f'kl_{self.latents.name}'
+    kl[key] = kl[key] + self.beta * eng.vamp_c.clone()
+    return llk, kl
+
+  def _step_metrics(self, out, metrics):
+    metrics[f'kl_{self.latents.name}'] = out[2] + out[3]   # beta * mean(kl_std + c)
+
+  def sample_prior(self, n: int = 1, seed: int = 1) -> torch.Tensor:
+    return self.vamprior.sample(n, seed=seed)
+
+  def _prior_log_prob(self, eng, z, lp):
+    eng.pseudo_forward()   # (one encoder pass at batch K, then all n * B samples in chunks)
+    eng.vamprior_log_prob(z.reshape(-1, z.shape[-1]), lp.reshape(-1))
 
 
 # ======================================================================================
@@ -1615,7 +1744,8 @@ class FactorVAE(AnnealingVAE):
 def get_vae(name: str):
   """odin/bay/vi/autoencoder/__init__.py:28"""
   table = {c.__name__.lower(): c for c in (VariationalAutoencoder, BetaVAE, AnnealingVAE,
-                                           BetaTCVAE, FactorVAE, BetaCapacityVAE, InfoVAE, DIPVAE)}
+                                           BetaTCVAE, FactorVAE, BetaCapacityVAE, InfoVAE, DIPVAE,
+                                           VampriorVAE)}
   table['vae'] = VariationalAutoencoder
   key = str(name).lower().replace('_', '')
   if key not in table:
