@@ -486,6 +486,26 @@ int odin_vamprior_fwd_bwd(const float* z, const float* pu, float* ws, float* c, 
  * hard_probs; scale: a constant factor of the chain between u and the tensor g was taken for, e.g. 2 for CenterAt0) */
 int odin_clip_range_fwd(const float* w, float* u, size_t n, float lo, float hi, void* stream);
 int odin_clip_range_bwd(const float* w, float* g, size_t n, float lo, float hi, float scale, void* stream);
+/* ---- VQVAE's vector quantiser (odin/bay/distributions/vector_quantizer.py, odin/bay/vi/autoencoder/vq_vae.py):
+ * codes [N, Cs] against codebook [K, Cs].
+ * odin_vq_assign: idx[n] = argmin_k sum_d (c_nd - e_kd)^2 (fp32 sum of squared differences, never the expanded form;
+ * ties: the smallest k), z_q = codebook[idx], m_out[0] = mean over all N Cs elements of (c - z_q)^2 (float64, fixed
+ * order: one partial per workgroup, then one workgroup), cnt[k] = #{n: idx_n = k} (optional: NULL for a forward-only
+ * call, which leaves the same idx, z_q and m bit for bit); zq_amax: range word of z_q (optional).  The codebook is
+ * staged in LDS once per workgroup.  ws: odin_vq_workspace(N) floats, 8-byte aligned, no initialisation needed.
+ * odin_vq_bwd: dcodes = (dz_q + 2 commitment / (N Cs) (codes - z_q)) * act'(codes) (straight through + commitment
+ * term; act: the activation that produced `codes`, 0 = none; dcodes_amax: its range word, optional) and, for the
+ * codebook, EITHER dcodebook[k] = 2 / (N Cs) sum_{n: idx_n = k} (e_k - c_n) (trained by gradient) OR the moving
+ * averages ema_counts <- decay ema_counts + (1 - decay) cnt, ema_means <- decay ema_means + (1 - decay) sum_k,
+ * codebook <- ema_means / (ema_counts + epsilon) written in place (no zero-debias); neither: dcodes only.  One
+ * workgroup per code sums its members in float64 in a fixed order.  No float atomics: bit-reproducible.
+ * Limits (a negative return code otherwise): N <= 65536, K <= 1024, Cs <= 256, K * Cs * 4 bytes <= 64 KB. */
+int odin_vq_workspace(int N);
+int odin_vq_assign(const float* codes, const float* codebook, int32_t* idx, float* z_q, float* ws, float* m_out,
+                   int32_t* cnt, uint32_t* zq_amax, int N, int K, int Cs, void* stream);
+int odin_vq_bwd(const float* codes, const float* z_q, const int32_t* idx, const float* dz_q, float* codebook,
+                float* dcodes, float* dcodebook, float* ema_counts, float* ema_means, float commitment, double decay,
+                double epsilon, int act, uint32_t* dcodes_amax, int N, int K, int Cs, void* stream);
 /* permute_dims (odin/bay/vi/utils.py:233-269): out[i,l] = z[perm[i,l], l]; perm int32 [B,D] */
 int odin_permute_dims(const float* z, const int32_t* perm, float* out, int B, int D, void* stream);
 /* per-column random permutations generated on device (Philox), perm int32 [B,D] */

@@ -139,6 +139,9 @@ SIGNATURES = {
     'odin_vamprior_fwd_bwd': [P, P, P, P, P, P, P, P, I, I, I, P],
     'odin_clip_range_fwd': [P, P, C.c_size_t, F, F, P],
     'odin_clip_range_bwd': [P, P, C.c_size_t, F, F, F, P],
+    'odin_vq_workspace': [I],
+    'odin_vq_assign': [P, P, P, P, P, P, P, P, I, I, I, P],
+    'odin_vq_bwd': [P, P, P, P, P, P, P, P, P, F, C.c_double, C.c_double, I, P, I, I, I, P],
     'odin_permute_dims': [P, P, P, I, I, P],
     'odin_random_perm': [P, I, I, C.c_uint64, P, P],
     'odin_random_permute_dims': [P, P, P, I, I, C.c_uint64, P, P],
@@ -179,7 +182,7 @@ SIGNATURES = {
 VALUE_RETURNING = ('odin_version', 'odin_comm_library', 'odin_conv2d_dgrad_keeps_range',
                    'odin_deconv2d_dgrad_keeps_range', 'odin_bernoulli_tail_keeps_range', 'odin_dense_dgrad_keeps_range', 'odin_conv2d_reads_x_range',
                    'odin_deconv2d_reads_x_range', 'odin_dense_reads_x_range', 'odin_max_slab_rows', 'odin_debug_absmax_fallbacks', 'odin_crc32c', 'odin_debug_last_path',
-                   'odin_latent_block_rows', 'odin_neck_rows', 'odin_debug_igemm_h_ldsw_steps', 'odin_total_correlation_workspace', 'odin_mmd_workspace', 'odin_dip_workspace', 'odin_vamprior_workspace', 'odin_debug_igemm_h_min_flop', 'odin_debug_blk_min_flop',
+                   'odin_latent_block_rows', 'odin_neck_rows', 'odin_debug_igemm_h_ldsw_steps', 'odin_total_correlation_workspace', 'odin_mmd_workspace', 'odin_dip_workspace', 'odin_vamprior_workspace', 'odin_vq_workspace', 'odin_debug_igemm_h_min_flop', 'odin_debug_blk_min_flop',
                    'odin_debug_blk_planes', 'odin_debug_blk_first', 'odin_debug_dense_hw_min_tiles', 'odin_gaussian_tail_applicable', 'odin_disc_head_rows', 'odin_debug_mel_r16', 'odin_debug_smallc_planes')
 # entry points declared `void` in include/odin_hip.h
 VOID_RETURNING = ('odin_wgrad_planes_defer_begin', 'odin_wgrad_pair_begin')

@@ -466,7 +466,9 @@ class VAEEngine:
                latent_reg: Optional[str] = None, reg_coef: float = 1.0, mmd_kernel: str = 'gaussian',
                mmd_prior_samples: int = 100, dip_lambda: Tuple[float, float] = (1.0, 2.0), prior_seed: int = 0,
                vamprior_components: Optional[int] = None, pseudoinputs_mean: float = -0.05,
-               pseudoinputs_std: float = 0.01, pseudoinputs=None):
+               pseudoinputs_std: float = 0.01, pseudoinputs=None,
+               vq_codes: Optional[int] = None, vq_code_size: Optional[int] = None, vq_commitment: float = 0.25,
+               vq_ema: bool = False, vq_ema_decay: float = 0.99, vq_epsilon: float = 1e-5, vq_state=None):
     """The keyword-only arguments are the engine's launch-order / A-B options (tests and tools pass them; the engine
     reads no environment variable):
       act_words        activation range words for the two-plane consumers; False: unscaled planes
@@ -502,7 +504,19 @@ class VAEEngine:
                            layout (key ('vamp', 'u')); the term beta * mean(c), c = log N(z; 0, I) - log p(z), is added to
                            the loss and reported as out4[3]; `kl` stays the standard-normal KL, `vamp_c` holds c [B]
       pseudoinputs_mean / pseudoinputs_std   W_u ~ Normal(mean, std) when the engine allocates its own parameters
-      pseudoinputs         an explicit [K, prod(in_shape)] array instead"""
+      pseudoinputs         an explicit [K, prod(in_shape)] array instead
+    The vector-quantised latent of VQVAE (vq.hip; excludes tc, latent_reg, vamprior_components, capacity,
+    free bits, data parallelism and an explicit neck_bwd; the neck, the latent block and the fused tail / head are not
+    planned; `zdim` is not used: the decoder reads z_q [B, H]):
+      vq_codes        None | K: the encoder's flat output h [B, H] is viewed as B * L codes of vq_code_size and replaced
+                      by its nearest codebook row; there is no ('lat', ...) entry in the parameter layout
+      vq_code_size    None (= H, one code per input) | Cs, a divisor of H
+      vq_commitment   weight of the commitment term; out4 = [loss, mean llk, beta * L * log K, commitment (+ latents)],
+                      out8[4] = m = mean (codes - z_q)^2
+      vq_ema          False: the codebook [K, Cs] is the LAST entry of the parameter layout (key ('vq', 'codebook')) and
+                      the `latents` term trains it; True: it lives outside the layout with ema_counts / ema_means and
+                      the step's backward launch moves it (decay vq_ema_decay, vq_epsilon in the denominator)
+      vq_state        (codebook, ema_counts, ema_means) of another engine of the same model (vq_ema=True only)"""
     self.lib = lib if lib is not None else _lib.load()
     self.device = torch.device(device)
     self.B, self.D = int(batch_size), int(zdim)
@@ -532,15 +546,30 @@ class VAEEngine:
     self.vamp_K = None if vamprior_components is None else int(vamprior_components)
     if self.vamp_K is not None:
       self._check_vamprior(analytic, reverse, free_bits, tc, latent_reg, capacity, range_words)
+    self.vq_K = None if vq_codes is None else int(vq_codes)
+    if self.vq_K is not None:
+      self._check_vq(free_bits, tc, latent_reg, capacity, range_words, neck_bwd)
+      self.vq_cw, self.vq_ema = float(vq_commitment), bool(vq_ema)
+      self.vq_decay, self.vq_eps = float(vq_ema_decay), float(vq_epsilon)
     f32 = dict(dtype=torch.float32, device=self.device)
     # ---- parameters ----
     self.layout = ParamLayout()
     self.enc_recs, eo = build_layers('enc', enc_layers, self.in_shape, self.layout)
     assert len(eo) == 1, 'encoder must end with a flat output'
     self.hdim = eo[0]
-    self.lat_w_off = self.layout.add(('lat', 'w'), (self.hdim, 2 * self.D))
-    self.lat_b_off = self.layout.add(('lat', 'b'), (2 * self.D,))
+    if self.vq_K is None:
+      self.lat_w_off = self.layout.add(('lat', 'w'), (self.hdim, 2 * self.D))
+      self.lat_b_off = self.layout.add(('lat', 'b'), (2 * self.D,))
+    else:
+      # no latent projection (VectorQuantizer has none): the decoder reads z_q [B, H]
+      self.lat_w_off = self.lat_b_off = 0
+      self.D = self.hdim
+      self._resolve_vq_code_size(vq_code_size)
     self.dec_recs, do = build_layers('dec', dec_layers, (self.D,), self.layout)
+    if self.vq_K is not None and not self.vq_ema:
+      # trained by gradient: one more parameter tensor behind the networks' (gradients, Adam moments, the norm, the NaN
+      # guard and the views cover it)
+      self.vq_cb_off = self.layout.add(('vq', 'codebook'), (self.vq_K, self.vq_Cs))
     if self.vamp_K is not None:
       # the pseudo-inputs: one more parameter tensor behind the networks', so that gradients, Adam moments, the norm,
       # the NaN guard and the checkpoint code see it like any other
@@ -575,6 +604,8 @@ class VAEEngine:
     # (VampPrior: the pseudo-input pass's gradient | activation words behind the data pass's, in the same buffer -- the
     # step's last backward launch clears them all)
     npw = 2 * ne if self.vamp_K is not None else 0
+    if self.vq_K is not None:
+      npw = 1   # (the word of z_q, right behind the activation words)
     self.range_words = (range_words if range_words is not None else
                         torch.zeros((2 * nl + npw) * RANGE_WORDS, dtype=torch.int32, device=self.device))
     assert self.range_words.numel() == (2 * nl + npw) * RANGE_WORDS
@@ -625,10 +656,11 @@ class VAEEngine:
     self.out8 = torch.zeros(8, **f32)
     self.out4 = self.out8[:4]
     self.n_part = 0
-    rows = C.c_int(0)
-    self.lib.odin_dense_wgrad(None, None, None, C.byref(rows), B, self.hdim, 2 * D, None)
-    self.lat_slab = torch.empty(rows.value, self.hdim * 2 * D + 2 * D, **f32)
-    self.lat_rows = rows.value
+    if self.vq_K is None:
+      rows = C.c_int(0)
+      self.lib.odin_dense_wgrad(None, None, None, C.byref(rows), B, self.hdim, 2 * D, None)
+      self.lat_slab = torch.empty(rows.value, self.hdim * 2 * D + 2 * D, **f32)
+      self.lat_rows = rows.value
     if tc == 'betatc':
       self.tc_ws = torch.zeros(self.lib.odin_total_correlation_workspace(
           B, B * self.world_size if self.tc_sharded else B, D), **f32)
@@ -645,11 +677,14 @@ class VAEEngine:
         self.tc_part_all = torch.empty(2, Bg, D, **f32)    # dloc / dscale partials for every i
     if latent_reg is not None:
       self._plan_latent_reg(f32, mmd_kernel, mmd_prior_samples, dip_lambda, prior_seed)
-    self._plan_fused_tail(f32)
-    self._plan_gauss_head(f32)
-    self._plan_latent_block(f32)
-    self._neck_bwd_opt = neck_bwd
-    self._plan_neck(f32, bool(neck))
+    if self.vq_K is None:
+      self._plan_fused_tail(f32)
+      self._plan_gauss_head(f32)
+      self._plan_latent_block(f32)
+      self._neck_bwd_opt = neck_bwd
+      self._plan_neck(f32, bool(neck))
+    else:
+      self._plan_vq(f32, own_params, vq_state)
     if self.vamp_K is not None:
       self._plan_vamprior(f32, mr, act_words, small_wgrad_gf)
     self.ws = torch.empty(4096, **f32)
@@ -905,6 +940,118 @@ class VAEEngine:
                             2.0 if self.enc_recs[0].center else 1.0, st)
     jobs.append(ReduceJob(self.vamp_du.data_ptr(), g0 + 4 * self.vamp_u_off, n_u, 1, n_u, 0))
     self._penc_words_dirty = False   # (cleared with the engine's words by the reduction that follows)
+
+  # ---- vector-quantised latent (vq_vae.py, vector_quantizer.py) -------------------------------------------
+  def _check_vq(self, free_bits, tc, latent_reg, capacity, range_words, neck_bwd):
+    K = self.vq_K
+    if not 1 <= K <= 1024:
+      raise ValueError(f'vq_codes={K}: the quantiser kernel takes 1 .. 1024 codes')
+    if tc is not None:
+      raise ValueError(f'vq_codes cannot be combined with tc={tc!r} (there is no Gaussian posterior)')
+    if latent_reg is not None:
+      raise ValueError(f'vq_codes cannot be combined with latent_reg={latent_reg!r} (there is no Gaussian posterior)')
+    if self.vamp_K is not None:
+      raise ValueError('vq_codes cannot be combined with vamprior_components (there is no Gaussian posterior)')
+    if free_bits is not None:
+      raise NotImplementedError('vq_codes with free_bits: the KL is the constant L * log K')
+    if capacity:
+      raise NotImplementedError('vq_codes with capacity=True (BetaCapacityVAE) is not offered')
+    if self.is_dp:
+      raise NotImplementedError('vq_codes under data parallelism (world_size > 1 / force_dp) is not offered')
+    if range_words is not None:
+      raise NotImplementedError('vq_codes with shared range_words is not offered')
+    if neck_bwd is not None:
+      raise NotImplementedError('vq_codes with neck_bwd: the fused neck needs the Gaussian latent block')
+
+  def _resolve_vq_code_size(self, code_size):
+    H, K = self.hdim, self.vq_K
+    Cs = H if code_size is None else int(code_size)
+    if Cs < 1 or H % Cs != 0:
+      raise ValueError(f'vq_code_size={code_size}: must divide the encoder output width {H}')
+    if Cs > 256 or K * Cs * 4 > 64 * 1024 or self.B * (H // Cs) > 65536:
+      raise ValueError(f'vq_codes={K}, vq_code_size={Cs}, batch_size={self.B}: outside the quantiser kernel '
+                       f'(Cs <= 256, K * Cs * 4 B <= 64 KB, B * L <= 65536)')
+    if self.enc_recs[-1].kind == 'deconv':
+      raise NotImplementedError('vq_codes: an encoder that ends in a Conv2DTranspose is not offered')
+    self.vq_Cs, self.vq_L = Cs, H // Cs
+
+  def _plan_vq(self, f32, own_params, vq_state):
+    K, Cs, L, B = self.vq_K, self.vq_Cs, self.vq_L, self.B
+    self.fused_tail, self.tail_mode = False, None
+    self.gauss_head = self._used_head = False
+    self.lat_block = self._used_block = False
+    self.neck = self._used_neck = False
+    self._neck_bwd_opt = None
+    self.vq_N = B * L
+    i32 = dict(dtype=torch.int32, device=self.device)
+    self.vq_idx = torch.zeros(self.vq_N, **i32)
+    self.vq_cnt = torch.zeros(K, **i32)
+    self.vq_ws = torch.zeros(self.lib.odin_vq_workspace(self.vq_N), **f32)
+    assert self.vq_ws.data_ptr() % 8 == 0
+    if self.vq_ema:
+      if vq_state is not None:
+        self.vq_codebook, self.vq_ema_counts, self.vq_ema_means = vq_state
+        assert tuple(self.vq_codebook.shape) == (K, Cs) and tuple(self.vq_ema_means.shape) == (K, Cs)
+      else:
+        self.vq_codebook = torch.empty(K, Cs, **f32)
+        self.vq_ema_means = torch.empty(K, Cs, **f32)
+        self.vq_ema_counts = torch.empty(K, **f32)
+        self.init_codebook()
+      self.vq_dcb = None
+    else:
+      assert vq_state is None, 'vq_state belongs to vq_ema=True: the codebook is a parameter otherwise'
+      self.vq_codebook = self.params[self.vq_cb_off:self.vq_cb_off + K * Cs].view(K, Cs)
+      self.vq_ema_counts = self.vq_ema_means = None
+      self.vq_dcb = torch.empty(1, K * Cs, **f32)   # d loss / d codebook: a one-row slab
+      if own_params:
+        self.init_codebook()
+    # KL(q || Multinomial(1, logits=0)) of a one-hot posterior: L * log K per input, whatever the input is
+    self.kl.fill_(L * math.log(K))
+    # the word of z_q for the decoder's first layer, where one of its launches reads planes
+    nl = len(self.enc_recs) + len(self.dec_recs)
+    self._vq_zq_word = None
+    if self.dec.reads_x[0]:
+      w = self.range_words.data_ptr() + 4 * RANGE_WORDS * 2 * nl
+      self._vq_zq_word = self.dec.x_word[0] = w
+      if self.dec.descs[0] is not None:
+        self.dec.descs[0].x_amax = w
+
+  def init_codebook(self, codebook=None):
+    """variance_scaling(distribution='uniform') over [K, Cs] (fan_in: the first axis): U(+-sqrt(3 / K)); or an explicit
+    array.  Under the moving average: ema_means = the codebook, ema_counts = 0."""
+    K, Cs = self.vq_K, self.vq_Cs
+    if codebook is not None:
+      a = torch.as_tensor(np.asarray(codebook, dtype=np.float32)).reshape(K, Cs)
+    else:
+      g = torch.Generator(device='cpu').manual_seed(self.seed + 0x7671)
+      a = (torch.rand(K, Cs, generator=g) * 2 - 1) * math.sqrt(3.0 / K)
+    self.vq_codebook.copy_(a.to(self.device))
+    if self.vq_ema:
+      self.vq_ema_means.copy_(self.vq_codebook)
+      self.vq_ema_counts.zero_()
+
+  def vq_state(self):
+    """(codebook, ema_counts, ema_means) for another engine of the same model (vq_ema=True)"""
+    return (self.vq_codebook, self.vq_ema_counts, self.vq_ema_means)
+
+  def _vq_assign(self, h_e, st, count: bool = True):
+    self.lib.odin_vq_assign(h_e.data_ptr(), self.vq_codebook.data_ptr(), self.vq_idx.data_ptr(), self.z.data_ptr(),
+                            self.vq_ws.data_ptr(), self.out8[4:].data_ptr(), self.vq_cnt.data_ptr() if count else None,
+                            self._vq_zq_word, self.vq_N, self.vq_K, self.vq_Cs, st)
+
+  def _vq_bwd(self, st, jobs):
+    """dz_q (the decoder's input gradient) -> the encoder's top gradient, straight through plus the commitment term,
+    and the codebook's gradient (a one-row slab) or its moving-average update"""
+    top = self.enc.set_top_word(True)
+    self.lib.odin_vq_bwd(self.enc.outs[-1].data_ptr(), self.z.data_ptr(), self.vq_idx.data_ptr(), self.dz.data_ptr(),
+                         self.vq_codebook.data_ptr(), self.enc.gouts[-1].data_ptr(),
+                         None if self.vq_ema else self.vq_dcb.data_ptr(),
+                         self.vq_ema_counts.data_ptr() if self.vq_ema else None,
+                         self.vq_ema_means.data_ptr() if self.vq_ema else None, self.vq_cw, self.vq_decay, self.vq_eps,
+                         ACT[self.enc_recs[-1].act], top, self.vq_N, self.vq_K, self.vq_Cs, st)
+    if not self.vq_ema:
+      n = self.vq_dcb.numel()
+      jobs.append(ReduceJob(self.vq_dcb.data_ptr(), self.grads[self.vq_cb_off:].data_ptr(), n, 1, n, 0))
 
   def _comm(self):
     if self.comm is None:
@@ -1216,6 +1363,9 @@ class VAEEngine:
       # VampPrior: the term beta * mean_b c_b; its gradient beta / B_global * d(sum_b c_b)
       h[H_TCCOEF] = beta
       h[H_TCGRAD] = beta / Bg
+    if self.vq_K is not None:
+      # VQVAE: the term (commitment weight (+ 1 for `latents`)) * m; its gradient is formed inside odin_vq_bwd
+      h[H_TCCOEF] = self.vq_cw + (0.0 if self.vq_ema else 1.0)
     if extra is not None:  # second optimiser's Adam block (FactorVAE discriminator), slots 10..14
       for i, val in enumerate(extra):
         h[10 + i] = float(val)
@@ -1294,7 +1444,9 @@ class VAEEngine:
       return
     if self._act_words_dirty:
       nl = len(self.enc_recs) + len(self.dec_recs)
-      self.lib.odin_range_reset(self.range_words.data_ptr() + 4 * RANGE_WORDS * nl, nl, st)
+      # (the quantiser's word of z_q sits right behind the activation words)
+      self.lib.odin_range_reset(self.range_words.data_ptr() + 4 * RANGE_WORDS * nl,
+                                nl + (1 if self.vq_K is not None else 0), st)
     self._act_words_dirty = True
 
   # ---- partial passes used by the model API (encode / decode) ---------------------------
@@ -1305,6 +1457,11 @@ class VAEEngine:
     assert x.shape == (B,) + self.in_shape and x.is_contiguous()
     self.x = x
     self._clear_stale_act_words(st)
+    if self.vq_K is not None:
+      # -> (codes, z_q), both [B, H]; vq_idx holds the assignments (a forward-only call of the quantiser)
+      h_e = self.enc.forward(x, st)
+      self._vq_assign(h_e, st, count=False)
+      return h_e, self.z
     lw = self.params[self.lat_w_off:]
     lb = self.params[self.lat_b_off:]
     if self.neck:
@@ -1348,6 +1505,10 @@ class VAEEngine:
     self._clear_stale_act_words(st)
     if len(self.dec_recs) > 1:
       self.dec.set_x_word(1, True)
+    if self.vq_K is not None and self._vq_zq_word is not None:
+      # (any [B, H] tensor; the quantiser's own output too, whose word the reset above may just have cleared: the word
+      # comes from one pass over whatever the decoder is about to read)
+      self.lib.odin_absmax(z.data_ptr(), z.numel(), self._vq_zq_word, st)
     return self.dec.forward(z, st)
 
   def observation_llk(self, h_d: torch.Tensor, x: torch.Tensor, out: torch.Tensor, st=None):
@@ -1422,6 +1583,10 @@ class VAEEngine:
                                 r0.N, ACT[r0.act], int(self.analytic), self.free_bits,
                                 self.hp(H_CAP) if self.capacity_on else None, st)
       dec_in, dec_start = self.dec.outs[0], 1
+    elif self.vq_K is not None:
+      h_e = self.enc.forward(x, st)
+      self._vq_assign(h_e, st)
+      dec_in, dec_start = self.z, 0
     else:
       if eps is None:
         lib.odin_rng_normal(self.eps.data_ptr(), B * D, self.seed, self.hp(N_HYPER), st)
@@ -1558,6 +1723,8 @@ class VAEEngine:
                                 self.vamp_c.data_ptr(), self.vamp_dz.data_ptr(), self.vamp_dpu.data_ptr(), None,
                                 self.hp(H_TCGRAD), B, self.vamp_K, D, st)
       tcp = self.vamp_ws.data_ptr()
+    elif self.vq_K is not None:
+      tcp = self.out8[4:].data_ptr()   # m, left by the quantiser; the finalisation multiplies it by H_TCCOEF
     self._llk_part_used = llk_part
     if tc_ptr is not None:
       tcp = tc_ptr
@@ -1744,7 +1911,10 @@ class VAEEngine:
     last = self.enc_recs[-1]
     aux_act = ACT[last.act]
     lw = self.params[self.lat_w_off:]
-    if self._bwd_neck():
+    if self.vq_K is not None:
+      assert extra_dz is None
+      self._vq_bwd(st, jobs)
+    elif self._bwd_neck():
       ne = len(self.enc_recs)
       self._neck_bwd(dzx, tl, ts, st, jobs)
       jobs += self.enc.backward(self.x, self.enc.gouts[ne - 3], st, fork=fork, last=ne - 3)
@@ -1964,7 +2134,8 @@ class VAEEngine:
         self.forward(x, eps, finalize=False, prior=prior)
         tcp = (self.tc_ws.data_ptr() if self.tc_mode == 'betatc' else
                self.reg_ws.data_ptr() if self.reg_mode is not None else
-               self.vamp_ws.data_ptr() if self.vamp_K is not None else None)
+               self.vamp_ws.data_ptr() if self.vamp_K is not None else
+               self.out8[4:].data_ptr() if self.vq_K is not None else None)
         self._fin_pending = (self._llk_part_used.data_ptr(), self.n_part, tcp)
       P.append(('k', fwd))
     if self.is_dp and self.dp_buckets >= 2:
@@ -2078,12 +2249,17 @@ class VAEEngine:
       cap.wait_stream(torch.cuda.current_stream(self.device))
       saved = (self.params.clone(), self.m.clone(), self.v.clone(), self.flag.clone(),
                self.skipped_update.clone(), self.hyper.clone())
+      # (the quantiser's moving averages are state the warm-up step advances too)
+      vq_saved = [t.clone() for t in self.vq_state()] if (self.vq_K is not None and self.vq_ema) else None
       with torch.cuda.stream(cap):
         sg.run_eager()
         # the warm-up step must not count: restore the optimiser state it touched (and the hyper-parameter row: with
         # the device ring the warm-up's Adam has already loaded the NEXT step's row)
         self.params.copy_(saved[0]); self.m.copy_(saved[1]); self.v.copy_(saved[2])
         self.flag.copy_(saved[3]); self.skipped_update.copy_(saved[4]); self.hyper.copy_(saved[5])
+        if vq_saved is not None:
+          for t, s0 in zip(self.vq_state(), vq_saved):
+            t.copy_(s0)
       torch.cuda.current_stream(self.device).wait_stream(cap)
       if self.side_stream is not None:
         torch.cuda.current_stream(self.device).wait_stream(self.side_stream)

@@ -410,7 +410,7 @@ class VariationalAutoencoder:
     deconv = {r.key for r in eng.enc_recs + eng.dec_recs if r.kind == 'deconv'}
     for key, shp, off in eng.layout.entries:
       n = int(np.prod(shp))
-      if key[0] == 'vamp':   # (the pseudo-inputs: drawn by the engine, VAEEngine._init_pseudoinputs)
+      if key[0] in ('vamp', 'vq'):   # (drawn by the engine: VAEEngine._init_pseudoinputs / init_codebook)
         continue
       if key[-1] == 'b':
         eng.params[off:off + n].zero_()
@@ -703,6 +703,8 @@ class VariationalAutoencoder:
     DistributionDense 'latents', dense_distribution.py:229-238) + /kernel | /bias."""
     if key[0] == 'vamp':
       return VAMPRIOR_VARIABLE
+    if key[0] == 'vq':
+      return f'{VQ_LAYER}/{key[1]}'
     suffix = 'kernel' if key[-1] == 'w' else 'bias'
     if key[0] == 'lat':
       return f'{self.latents.name}/{suffix}'
@@ -1193,6 +1195,252 @@ class VampriorVAE(BetaVAE):
   def _prior_log_prob(self, eng, z, lp):
     eng.pseudo_forward()   # (one encoder pass at batch K, then all n * B samples in chunks)
     eng.vamprior_log_prob(z.reshape(-1, z.shape[-1]), lp.reshape(-1))
+
+
+# layer name of the quantiser (vq_vae.py:272-281): its variables are VQLatents/codebook and, under the moving average,
+# VQLatents/ema_counts and VQLatents/ema_means
+VQ_LAYER = 'VQLatents'
+
+
+class MultinomialPrior:
+  """Multinomial(1, logits=0) over the K codes (vector_quantizer.py:110-120): the prior of every code position.  The
+  reference's `trainable_prior` creates the logits as a variable, but the KL is taken under stop_gradient: nothing
+  ever trains them.  Kept as zeros."""
+
+  def __init__(self, n_codes: int):
+    self.n_codes = int(n_codes)
+    self.logits = torch.zeros(self.n_codes)
+
+  def log_prob(self, one_hot: torch.Tensor) -> torch.Tensor:
+    return -math.log(self.n_codes) * one_hot.sum(-1)
+
+
+class VectorQuantizedPosterior:
+  """vector_quantizer.py (VectorQuantized): codes [B, L, Cs], their assignments [B, L] and nearest codebook rows.
+  tensor() / sample() give the value of the straight-through sample, z_q viewed [B, L * Cs]."""
+
+  def __init__(self, codes: torch.Tensor, assignments: torch.Tensor, nearest: torch.Tensor, n_codes: int,
+               commitment_weight: float):
+    self.codes, self.assignments, self.nearest_codes = codes, assignments, nearest
+    self.n_codes, self.commitment_weight = int(n_codes), float(commitment_weight)
+
+  def one_hot(self) -> torch.Tensor:
+    return torch.nn.functional.one_hot(self.assignments.long(), self.n_codes).to(torch.float32)
+
+  @property
+  def latents_loss(self) -> torch.Tensor:
+    return ((self.codes - self.nearest_codes) ** 2).mean()
+
+  @property
+  def commitment_loss(self) -> torch.Tensor:
+    return self.commitment_weight * self.latents_loss
+
+  def tensor(self) -> torch.Tensor:
+    return self.nearest_codes.reshape(self.nearest_codes.shape[0], -1)
+
+  def sample(self, n=None, seed=None) -> torch.Tensor:
+    return self.tensor()
+
+  def mean(self) -> torch.Tensor:
+    return self.tensor()
+
+  def __array__(self):
+    return self.tensor().cpu().numpy()
+
+
+class VectorQuantizer:
+  """vector_quantizer.py:60-200: the configuration of the quantiser and its codebook (held by the model's engines).
+  `distance_metric`: 'euclidean' only; `trainable_prior`: accepted, without effect (see MultinomialPrior)."""
+
+  def __init__(self, vae: 'VQVAE', n_codes: int = 64, commitment_weight: float = 0.25,
+               distance_metric: str = 'euclidean', trainable_prior: bool = False, ema_decay: float = 0.99,
+               ema_update: bool = False, epsilon: float = 1e-5, code_size: Optional[int] = None,
+               name: str = 'VectorQuantizer'):
+    if str(distance_metric) != 'euclidean':
+      raise NotImplementedError(f"distance_metric={distance_metric!r}: the HIP quantiser offers 'euclidean'")
+    self._vae = vae
+    self.n_codes, self.commitment_weight = int(n_codes), float(commitment_weight)
+    self.distance_metric, self.trainable_prior = str(distance_metric), bool(trainable_prior)
+    self.ema_decay, self.ema_update, self.epsilon = float(ema_decay), bool(ema_update), float(epsilon)
+    self._code_size = None if code_size is None else int(code_size)
+    self.name = name
+    self.prior = MultinomialPrior(self.n_codes)
+
+  @property
+  def code_size(self) -> int:
+    return self._vae._engine(1).vq_Cs
+
+  @property
+  def codebook(self) -> torch.Tensor:
+    """the live [n_codes, code_size] tensor (every engine of the model reads this storage)"""
+    return self._vae._engine(1).vq_codebook
+
+  def _assign(self, codes: torch.Tensor):
+    eng = self._vae._engine(1)
+    c = _as_tensor(codes, self._vae.device).reshape(-1, eng.vq_Cs).contiguous()
+    N = c.shape[0]
+    idx = torch.empty(N, dtype=torch.int32, device=c.device)
+    zq = torch.empty_like(c)
+    step = min(N, 65536)
+    ws = torch.zeros(eng.lib.odin_vq_workspace(step), dtype=torch.float32, device=c.device)
+    m = torch.zeros(2, dtype=torch.float32, device=c.device)
+    for i0 in range(0, N, step):
+      n = min(step, N - i0)
+      eng.lib.odin_vq_assign(c[i0:].data_ptr(), eng.vq_codebook.data_ptr(), idx[i0:].data_ptr(), zq[i0:].data_ptr(),
+                             ws.data_ptr(), m.data_ptr(), None, None, n, eng.vq_K, eng.vq_Cs, eng.stream())
+    return idx, zq
+
+  def sample_indices(self, codes) -> torch.Tensor:
+    """nearest-code indices of codes [..., code_size] (ties: the smallest index)"""
+    shp = tuple(np.shape(codes))[:-1]
+    return self._assign(codes)[0].reshape(shp)
+
+  def sample_nearest(self, codes) -> torch.Tensor:
+    """the nearest codebook rows, same shape as `codes`"""
+    return self._assign(codes)[1].reshape(tuple(np.shape(codes)))
+
+  def sample(self, n: int = 1, seed: Optional[int] = None) -> torch.Tensor:
+    """n codebook rows at indices drawn uniformly (the prior is Multinomial(1, logits=0))"""
+    g = torch.Generator(device='cpu')
+    if seed is not None:
+      g.manual_seed(int(seed))
+    ids = torch.randint(0, self.n_codes, (int(n),), generator=g)
+    return self.codebook[ids.to(self._vae.device)].clone()
+
+
+class VQVAE(BetaVAE):
+  """vq_vae.py:249-330 (van den Oord et al. 2017): the encoder's flat output h [B, H] is viewed as L = H / code_size
+  codes, each replaced by its nearest codebook row; the decoder reads z_q [B, H] (there is no latent projection).
+  loss = -mean llk + beta * L * log K + commitment (+ latents without the moving average).  The reference overrides
+  `_elbo`, which its base class never calls, so as shipped the two VQ terms are never added; here elbo_components
+  returns them and the step is the one VQVAEStep describes.  `code_size=None`: one code per input
+  (what the reference does with the image networks).  Not offered: analytic=False (ValueError, as the reference),
+  free_bits, sample_shape other than (), marginal_log_prob (the posterior has no density), data parallelism."""
+
+  def __init__(self, n_codes: int = 64, commitment_weight: float = 0.25, distance_metric: str = 'euclidean',
+               trainable_prior: bool = False, ema_decay: float = 0.99, ema_update: bool = False,
+               beta: Union[float, Interpolation] = 1.0, epsilon: float = 1e-5, code_size: Optional[int] = None,
+               name='VQVAE', **kwargs):
+    analytic = kwargs.pop('analytic', True)
+    if not analytic:
+      raise ValueError('VQVAE only support analytic KL-divergence.')
+    ss = kwargs.get('sample_shape', ())
+    if isinstance(ss, int) or tuple(ss) != ():
+      raise NotImplementedError(f'VQVAE with sample_shape={ss!r}: one assignment per code only')
+    if kwargs.get('free_bits') is not None:
+      raise NotImplementedError('VQVAE with free_bits: the KL is the constant L * log K')
+    self._quantizer = VectorQuantizer(self, n_codes=n_codes, commitment_weight=commitment_weight,
+                                      distance_metric=distance_metric, trainable_prior=trainable_prior,
+                                      ema_decay=ema_decay, ema_update=ema_update, epsilon=epsilon, code_size=code_size,
+                                      name=VQ_LAYER)
+    super().__init__(beta=beta, name=name, analytic=True, **kwargs)
+
+  # ---- the quantiser ----
+  @property
+  def quantizer(self) -> VectorQuantizer:
+    return self._quantizer
+
+  @property
+  def codebook(self) -> torch.Tensor:
+    return self._quantizer.codebook
+
+  @property
+  def ema_update(self) -> bool:
+    return self._quantizer.ema_update
+
+  @property
+  def ema_counts(self) -> Optional[torch.Tensor]:
+    return self._engine(1).vq_ema_counts
+
+  @property
+  def ema_means(self) -> Optional[torch.Tensor]:
+    return self._engine(1).vq_ema_means
+
+  def _reg_options(self) -> dict:
+    q = self._quantizer
+    # (the moving-average state lives outside the parameter buffer: later engines share the first one's tensors)
+    first = next(iter(self._engines.values()), None)
+    return dict(vq_codes=q.n_codes, vq_code_size=q._code_size, vq_commitment=q.commitment_weight, vq_ema=q.ema_update,
+                vq_ema_decay=q.ema_decay, vq_epsilon=q.epsilon,
+                vq_state=first.vq_state() if (first is not None and q.ema_update) else None)
+
+  def set_elbo_configs(self, analytic=None, reverse=None, free_bits=None, sample_shape=None):
+    if analytic is False:
+      raise ValueError('VQVAE only support analytic KL-divergence.')
+    if free_bits is not None or sample_shape not in (None, ()):
+      raise NotImplementedError('VQVAE: free_bits and sample_shape are not offered')
+    return super().set_elbo_configs(analytic, reverse, free_bits, sample_shape)
+
+  # ---- forward API ----
+  def _posterior(self, eng: VAEEngine) -> VectorQuantizedPosterior:
+    B, L, Cs = eng.B, eng.vq_L, eng.vq_Cs
+    return VectorQuantizedPosterior(eng.enc.outs[-1].clone().reshape(B, L, Cs), eng.vq_idx.clone().reshape(B, L),
+                                    eng.z.clone().reshape(B, L, Cs), eng.vq_K, eng.vq_cw)
+
+  def decode(self, latents, training=None, mask=None, only_decoding=False, **kwargs):
+    z = latents.tensor() if isinstance(latents, VectorQuantizedPosterior) else latents
+    z = _as_tensor(z, self.device)
+    z = z.reshape(z.shape[0], -1).contiguous()
+    eng = self._engine(z.shape[0])
+    h = eng.run_decoder(z).clone()
+    return h if only_decoding else self._observation_dist(h)
+
+  def _vq_terms(self, eng: VAEEngine, m: torch.Tensor) -> Dict[str, torch.Tensor]:
+    lat, q = self.latents.name, self._quantizer
+    kl = {f'kl_{lat}': torch.full((), self.beta * eng.vq_L * math.log(q.n_codes), dtype=torch.float32,
+                                  device=self.device),
+          f'commitment_{lat}': q.commitment_weight * m}
+    if not q.ema_update:
+      kl[f'latents_{lat}'] = m.clone()
+    return kl
+
+  def elbo_components(self, inputs, training=None, mask=None, eps=None, **kwargs):
+    """llk [B] and the scalar terms kl_<latents> = beta * L * log K, commitment_<latents> and (codebook trained by
+    gradient) latents_<latents>; mean(elbo(llk, kl)) = -loss"""
+    x = _as_tensor(inputs, self.device)
+    eng = self._engine(x.shape[0])
+    eng.set_hyper(beta=self.beta, t=self._step)
+    eng.forward(x)
+    qz_x = self._posterior(eng)
+    px_z = self._observation_dist(eng.dec.outs[-1].clone())
+    self._last_outputs = (px_z, qz_x)
+    llk = {f'llk_{self.observation.name}': eng.llk.clone()}
+    return llk, self._vq_terms(eng, eng.out8[4].clone())
+
+  def _step_metrics(self, out, metrics):
+    q = self._quantizer
+    coef = q.commitment_weight + (0.0 if q.ema_update else 1.0)   # out[3] = coef * m
+    m = out[3] / coef if coef > 0 else torch.zeros_like(out[3])
+    lat = self.latents.name
+    metrics[f'commitment_{lat}'] = q.commitment_weight * m
+    if not q.ema_update:
+      metrics[f'latents_{lat}'] = m
+
+  def sample_prior(self, n: int = 1, seed: int = 1) -> torch.Tensor:
+    """[n, H]: L codebook rows per sample at uniformly drawn indices"""
+    eng = self._engine(1)
+    return self._quantizer.sample(int(n) * eng.vq_L, seed=seed).reshape(int(n), eng.hdim)
+
+  def marginal_log_prob(self, *args, **kwargs):
+    raise NotImplementedError('VQVAE.marginal_log_prob: the quantised posterior has no density')
+
+  # ---- checkpoints: the moving-average form keeps its three tensors outside the parameter buffer ----
+  def _extra_checkpoint_variables(self) -> Dict[str, np.ndarray]:
+    if not self.ema_update:
+      return {}
+    eng = self._engine(1)
+    return {f'{VQ_LAYER}/{n}': t.detach().cpu().numpy()
+            for n, t in zip(('codebook', 'ema_counts', 'ema_means'), eng.vq_state())}
+
+  def _load_extra_checkpoint_variables(self, d: Dict[str, np.ndarray]):
+    if not self.ema_update:
+      return
+    eng = self._engine(1)
+    for n, t in zip(('codebook', 'ema_counts', 'ema_means'), eng.vq_state()):
+      a = self._find_variable(d, f'{VQ_LAYER}/{n}')
+      if tuple(a.shape) != tuple(t.shape):
+        raise ValueError(f'{VQ_LAYER}/{n}: checkpoint shape {a.shape} != {tuple(t.shape)}')
+      t.copy_(torch.as_tensor(np.asarray(a), dtype=torch.float32, device=self.device))
 
 
 # ======================================================================================
@@ -1745,7 +1993,7 @@ def get_vae(name: str):
   """odin/bay/vi/autoencoder/__init__.py:28"""
   table = {c.__name__.lower(): c for c in (VariationalAutoencoder, BetaVAE, AnnealingVAE,
                                            BetaTCVAE, FactorVAE, BetaCapacityVAE, InfoVAE, DIPVAE,
-                                           VampriorVAE)}
+                                           VampriorVAE, VQVAE)}
   table['vae'] = VariationalAutoencoder
   key = str(name).lower().replace('_', '')
   if key not in table:
