@@ -203,7 +203,7 @@ __device__ __forceinline__ unsigned hash3(unsigned a, unsigned b, unsigned c) {
   return h;
 }
 
-// one workgroup per latent column: random keys -> rank -> permutation (B <= 4096)
+// one workgroup per latent column: random keys -> rank -> permutation (B <= 16384: the B keys in LDS, 64 KB)
 // (z != null: out[rank][l] = z[i][l] in the same pass -- permute_dims without a launch of its own)
 __global__ __launch_bounds__(256) void random_perm_kernel(int* perm, int B, int D, unsigned k0,
                                                           unsigned k1, const int* step_dev, const float* z, float* out) {
