@@ -15,7 +15,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Callable, Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -445,6 +445,19 @@ MMD_KERNELS = {'gaussian': 0, 'linear': 1}   # odin_mmd_fwd_bwd's `kernel`
 PRIOR_KEY_SALT = 0x6D6D6470 << 32            # high word of the prior stream's Philox key (eps streams: seed < 2^32)
 
 
+class LatentTerm(NamedTuple):
+  """The ONE term a step adds to the loss beside log-likelihood and KL, resolved at planning time (_plan_term): beta-TC,
+  MMD, DIP, VampPrior's c, the quantiser's commitment -- or none."""
+  value: Optional[torch.Tensor] = None    # its first float is what odin_elbo_finalize scales by H_TCCOEF
+  dz: Optional[torch.Tensor] = None       # the three gradient inputs of the latent backward
+  dloc: Optional[torch.Tensor] = None
+  dscale: Optional[torch.Tensor] = None
+  launch: Optional[Callable] = None       # launch(st): evaluates the term (and those gradients) behind the forward pass
+
+  def ptr(self) -> Optional[int]:
+    return None if self.value is None else self.value.data_ptr()
+
+
 class VAEEngine:
   """encoder -> q(z|x) -> decoder -> ELBO -> backward -> Adam for a FIXED batch size.
 
@@ -636,20 +649,8 @@ class VAEEngine:
     n_per = int(np.prod(self.in_shape))
     self.n_per = n_per
     # per-sample partial log-likelihoods: the kernel reports how many it writes per sample
-    npart = C.c_int(0)
-    if observation == 'bernoulli':
-      self.lib.odin_elbo_bernoulli_fwd_bwd(None, None, None, None, None, B, n_per, C.byref(npart),
-                                           None)
-    elif observation == 'mixqlogistic':
-      Cc = self.in_shape[-1]
-      self.lib.odin_elbo_mixqlogistic_fwd_bwd(None, None, None, None, None, B, n_per // Cc, Cc,
-                                              MIXQL_K, C.byref(npart), None)
-    else:
-      Cc = self.in_shape[-1]
-      self.lib.odin_elbo_gaussian_fwd_bwd(None, None, None, None, None, B, n_per // Cc, Cc,
-                                          OBS_MODE[observation],
-                                          C.byref(npart), None)
-    self.llk_part = torch.empty(B * max(npart.value, (n_per + 1023) // 1024), **f32)
+    npart = self._observation_fwd_bwd(None, None, None, None, None, None)
+    self.llk_part = torch.empty(B * max(npart, (n_per + 1023) // 1024), **f32)
     self.llk = torch.empty(B, **f32)
     # [loss, mean llk, mean beta*kl, tc | 4 spare words a model may place its own step scalars in (FactorVAE: dtc_loss),
     # so that ONE device-to-device copy snapshots them all]
@@ -687,6 +688,7 @@ class VAEEngine:
       self._plan_vq(f32, own_params, vq_state)
     if self.vamp_K is not None:
       self._plan_vamprior(f32, mr, act_words, small_wgrad_gf)
+    self._term = self._plan_term()
     self.ws = torch.empty(4096, **f32)
     self.gnorm2 = torch.zeros(1, **f32)
     self.flag = torch.zeros(1, dtype=torch.int32, device=self.device)
@@ -778,6 +780,55 @@ class VAEEngine:
       self.dip_blocks = self.reg_ws[4 + bs:4 + bs + W * bs]
     self._prior_explicit = False
 
+  def _plan_term(self) -> LatentTerm:
+    """at most one of tc / latent_reg / vamprior_components / vq_codes is on (the constructor's checks)"""
+    if self.tc_mode == 'betatc':
+      return LatentTerm(self.tc_ws, self.tc_dz, self.tc_dloc, self.tc_dscale,
+                        self._tc_global if self.tc_sharded else self._tc_local)
+    if self.reg_mode == 'mmd':
+      return LatentTerm(self.reg_ws, dz=self.reg_dz, launch=self._reg_global if self.reg_sharded else self._mmd_local)
+    if self.reg_mode is not None:
+      return LatentTerm(self.reg_ws, dloc=self.reg_dloc, dscale=self.reg_dscale if self.dip_type2 else None,
+                        launch=self._reg_global if self.reg_sharded else self._dip_local)
+    if self.vamp_K is not None:
+      return LatentTerm(self.vamp_ws, dz=self.vamp_dz, launch=self._vamp_term)
+    if self.vq_K is not None:
+      return LatentTerm(self.out8[4:])   # m, left by the quantiser (its gradient is formed inside odin_vq_bwd)
+    return LatentTerm()
+
+  def _tc_local(self, st):
+    self.lib.odin_total_correlation_fwd_bwd(self.z.data_ptr(), self.p.data_ptr(), self.tc_ws.data_ptr(),
+                                            self.tc_dz.data_ptr(), self.tc_dloc.data_ptr(), self.tc_dscale.data_ptr(),
+                                            self.hp(H_TCGRAD), self.B, self.D, st)
+
+  def _tc_global(self, st):
+    self._tc_pack()
+    self._tc_gather()
+    self._tc_shard(st)
+    self._tc_scatter()
+
+  def _mmd_local(self, st):
+    self.lib.odin_mmd_fwd_bwd(self.z.data_ptr(), self._prior_ptr(), self.reg_ws.data_ptr(), self.reg_dz.data_ptr(),
+                              None, self.hp(H_TCGRAD), self.B, self.mmd_M, self.D, self.mmd_kernel, self.prior_key,
+                              self.hp(N_HYPER), st)
+
+  def _dip_local(self, st):
+    self.lib.odin_dip_fwd_bwd(self.p.data_ptr(), self.reg_ws.data_ptr(), self.reg_dloc.data_ptr(),
+                              self.reg_dscale.data_ptr() if self.dip_type2 else None, None, self.hp(H_TCGRAD), self.B,
+                              self.D, self.dip_type2, self.dip_lambda[0], self.dip_lambda[1], st)
+
+  def _reg_global(self, st):
+    if self.reg_mode != 'mmd':
+      self._dip_moments(st)
+    for _, fn in self._reg_segments():
+      fn()
+
+  def _vamp_term(self, st):
+    # (the value unscaled: the finalisation multiplies it by H_TCCOEF = beta, once)
+    self.lib.odin_vamprior_fwd_bwd(self.z.data_ptr(), self.vamp_pu.data_ptr(), self.vamp_ws.data_ptr(),
+                                   self.vamp_c.data_ptr(), self.vamp_dz.data_ptr(), self.vamp_dpu.data_ptr(), None,
+                                   self.hp(H_TCGRAD), self.B, self.vamp_K, self.D, st)
+
   # ---- VampPrior (vamprior.py:25-107; DESIGN 3.13) --------------------------------------------------------------------
   VAMP_CLIP = (1e-6, 1.0 - 1e-6)   # hard_probs: clip_by_value(W_u, 1e-6, 1 - 1e-6)
 
@@ -787,23 +838,32 @@ class VAEEngine:
       raise ValueError(f'vamprior_components={K}: the mixture kernel takes 1 .. 1024 components')
     if not 1 <= self.B <= 4096 or not 1 <= self.D <= 64:
       raise ValueError(f'vamprior_components: batch_size={self.B}, zdim={self.D} outside the kernel (4096, 64)')
-    if tc is not None:
-      raise ValueError(f'vamprior_components cannot be combined with tc={tc!r} (the same step scalars)')
-    if latent_reg is not None:
-      raise ValueError(f'vamprior_components cannot be combined with latent_reg={latent_reg!r} (the same step scalars)')
+    self._check_no_term('vamprior_components', 'the same step scalars', tc, latent_reg)
     # (reverse=False without analytic=True never gets here: set_kl_form has raised TypeError)
     if not reverse:
       raise NotImplementedError('vamprior_components with reverse=False: KL(p || q) needs samples of the mixture')
     if analytic:
       raise NotImplementedError('vamprior_components with analytic=True: the KL to a mixture has no closed form')
+    self._check_plain_kl('vamprior_components', 'the clamp acts on the standard-normal KL only', free_bits, capacity,
+                         range_words)
+
+  # what a model with a latent term of its own (`what`: its keyword) shares with no other option, in two parts: each
+  # model has checks of its own between them, and the first failing check names the error
+  def _check_no_term(self, what, why, tc, latent_reg):
+    if tc is not None:
+      raise ValueError(f'{what} cannot be combined with tc={tc!r} ({why})')
+    if latent_reg is not None:
+      raise ValueError(f'{what} cannot be combined with latent_reg={latent_reg!r} ({why})')
+
+  def _check_plain_kl(self, what, why_free_bits, free_bits, capacity, range_words):
     if free_bits is not None:
-      raise NotImplementedError('vamprior_components with free_bits: the clamp acts on the standard-normal KL only')
+      raise NotImplementedError(f'{what} with free_bits: {why_free_bits}')
     if capacity:
-      raise NotImplementedError('vamprior_components with capacity=True (BetaCapacityVAE) is not offered')
+      raise NotImplementedError(f'{what} with capacity=True (BetaCapacityVAE) is not offered')
     if self.is_dp:
-      raise NotImplementedError('vamprior_components under data parallelism (world_size > 1 / force_dp) is not offered')
+      raise NotImplementedError(f'{what} under data parallelism (world_size > 1 / force_dp) is not offered')
     if range_words is not None:
-      raise NotImplementedError('vamprior_components with shared range_words is not offered')
+      raise NotImplementedError(f'{what} with shared range_words is not offered')
 
   def _init_pseudoinputs(self, pseudoinputs, mean, std):
     K, n = self.vamp_K, int(np.prod(self.in_shape))
@@ -935,10 +995,9 @@ class VAEEngine:
     # dW_u = du * [1e-6 < W_u < 1 - 1e-6], one complete slab row.  (The library's input gradient of a layer that
     # centres its input, 2 x - 1, is taken with respect to the centred tensor: the factor 2 joins here.)
     lo, hi = self.VAMP_CLIP
-    n_u = self.vamp_du.numel()
-    lib.odin_clip_range_bwd(self.params[self.vamp_u_off:].data_ptr(), self.vamp_du.data_ptr(), n_u, lo, hi,
-                            2.0 if self.enc_recs[0].center else 1.0, st)
-    jobs.append(ReduceJob(self.vamp_du.data_ptr(), g0 + 4 * self.vamp_u_off, n_u, 1, n_u, 0))
+    lib.odin_clip_range_bwd(self.params[self.vamp_u_off:].data_ptr(), self.vamp_du.data_ptr(), self.vamp_du.numel(),
+                            lo, hi, 2.0 if self.enc_recs[0].center else 1.0, st)
+    jobs.append(self._slab_job(self.vamp_du, self.vamp_u_off, 1))
     self._penc_words_dirty = False   # (cleared with the engine's words by the reduction that follows)
 
   # ---- vector-quantised latent (vq_vae.py, vector_quantizer.py) -------------------------------------------
@@ -946,20 +1005,10 @@ class VAEEngine:
     K = self.vq_K
     if not 1 <= K <= 1024:
       raise ValueError(f'vq_codes={K}: the quantiser kernel takes 1 .. 1024 codes')
-    if tc is not None:
-      raise ValueError(f'vq_codes cannot be combined with tc={tc!r} (there is no Gaussian posterior)')
-    if latent_reg is not None:
-      raise ValueError(f'vq_codes cannot be combined with latent_reg={latent_reg!r} (there is no Gaussian posterior)')
+    self._check_no_term('vq_codes', 'there is no Gaussian posterior', tc, latent_reg)
     if self.vamp_K is not None:
       raise ValueError('vq_codes cannot be combined with vamprior_components (there is no Gaussian posterior)')
-    if free_bits is not None:
-      raise NotImplementedError('vq_codes with free_bits: the KL is the constant L * log K')
-    if capacity:
-      raise NotImplementedError('vq_codes with capacity=True (BetaCapacityVAE) is not offered')
-    if self.is_dp:
-      raise NotImplementedError('vq_codes under data parallelism (world_size > 1 / force_dp) is not offered')
-    if range_words is not None:
-      raise NotImplementedError('vq_codes with shared range_words is not offered')
+    self._check_plain_kl('vq_codes', 'the KL is the constant L * log K', free_bits, capacity, range_words)
     if neck_bwd is not None:
       raise NotImplementedError('vq_codes with neck_bwd: the fused neck needs the Gaussian latent block')
 
@@ -1050,8 +1099,7 @@ class VAEEngine:
                          self.vq_ema_means.data_ptr() if self.vq_ema else None, self.vq_cw, self.vq_decay, self.vq_eps,
                          ACT[self.enc_recs[-1].act], top, self.vq_N, self.vq_K, self.vq_Cs, st)
     if not self.vq_ema:
-      n = self.vq_dcb.numel()
-      jobs.append(ReduceJob(self.vq_dcb.data_ptr(), self.grads[self.vq_cb_off:].data_ptr(), n, 1, n, 0))
+      jobs.append(self._slab_job(self.vq_dcb, self.vq_cb_off, 1))
 
   def _comm(self):
     if self.comm is None:
@@ -1265,22 +1313,23 @@ class VAEEngine:
     A.dh4_amax, A.dy3_amax, A.dx_amax = self.enc.set_top_word(True), self.enc.word(ne - 2), self.enc.word(ne - 3)
     A.slab1, A.slab0, A.slabl = self.nk_slab1.data_ptr(), self.nk_slab0.data_ptr(), self.nk_slabl.data_ptr()
     lib.odin_neck_bwd(C.byref(A), st)
-    rows = self.nk_rows
     for slab, off in ((self.nk_slab1, t1.w_off), (self.nk_slab0, d0.w_off), (self.nk_slabl, self.lat_w_off)):
-      jobs.append(ReduceJob(slab.data_ptr(), self.grads[off:].data_ptr(), slab.shape[1], rows, slab.shape[1], 0))
+      jobs.append(self._slab_job(slab, off, self.nk_rows))
     # conv3's weight gradient (a reduction over all B * 16 pixels) and the projection's (over the batch)
     wrows = C.c_int(0)
     lib.odin_wgrad_pair_begin()   # (independent of each other: one launch where both are small-layer implicit GEMMs)
-    slab = self.enc.wslabs[ne - 2]
-    lib.odin_conv2d_wgrad(self.enc.outs[ne - 3].data_ptr(), self.enc.gouts[ne - 2].data_ptr(), slab.data_ptr(),
-                          C.byref(wrows), C.byref(self.enc.descs[ne - 2]), st)
-    jobs.append(ReduceJob(slab.data_ptr(), self.grads[c3.w_off:].data_ptr(), slab.shape[1], wrows.value, slab.shape[1], 0))
-    slab = self.enc.wslabs[ne - 1]
-    lib.odin_dense_bwd_ranged(self.enc.outs[ne - 2].data_ptr(), self.enc.gouts[ne - 1].data_ptr(), None, None, 0, None,
-                              None, None, slab.data_ptr(), C.byref(wrows), self.B, d4.K, d4.N, 1, 0,
-                              self.enc.dy_word[ne - 1], None, None, st)
-    lib.odin_wgrad_pair_end()
-    jobs.append(ReduceJob(slab.data_ptr(), self.grads[d4.w_off:].data_ptr(), slab.shape[1], wrows.value, slab.shape[1], 0))
+    try:
+      slab = self.enc.wslabs[ne - 2]
+      lib.odin_conv2d_wgrad(self.enc.outs[ne - 3].data_ptr(), self.enc.gouts[ne - 2].data_ptr(), slab.data_ptr(),
+                            C.byref(wrows), C.byref(self.enc.descs[ne - 2]), st)
+      jobs.append(self._slab_job(slab, c3.w_off, wrows.value))
+      slab = self.enc.wslabs[ne - 1]
+      lib.odin_dense_bwd_ranged(self.enc.outs[ne - 2].data_ptr(), self.enc.gouts[ne - 1].data_ptr(), None, None, 0, None,
+                                None, None, slab.data_ptr(), C.byref(wrows), self.B, d4.K, d4.N, 1, 0,
+                                self.enc.dy_word[ne - 1], None, None, st)
+    finally:
+      lib.odin_wgrad_pair_end()   # (a launch that failed inside the pair must not leave it open for the next step)
+    jobs.append(self._slab_job(slab, d4.w_off, wrows.value))
 
   def _bwd_neck(self) -> bool:
     if not (self.neck and self._used_neck) or (self.is_dp and self.dp_buckets >= 2):
@@ -1296,6 +1345,11 @@ class VAEEngine:
     return self.lat_block and self._used_block and not (self.is_dp and self.dp_buckets >= 2)
 
   # ---- helpers -----------------------------------------------------------------------
+  def _slab_job(self, slab, off, rows, n=None) -> ReduceJob:
+    """the sum of the first `rows` rows of `slab` -> grads[off : off + n] (n: the slab's whole width by default)"""
+    return ReduceJob(slab.data_ptr(), self.grads[off:].data_ptr(), slab.shape[1] if n is None else n, rows,
+                     slab.shape[1], 0)
+
   def hp(self, idx):  # device address of one hyper scalar
     return self.hyper.data_ptr() + 4 * idx
 
@@ -1452,31 +1506,35 @@ class VAEEngine:
   # ---- partial passes used by the model API (encode / decode) ---------------------------
   def run_encoder(self, x: torch.Tensor, eps: Optional[torch.Tensor] = None, st=None):
     """encoder -> Dense(2D) -> (loc, softplus(raw)) -> z = loc + scale*eps; fills p, z, kl."""
-    lib, B, D = self.lib, self.B, self.D
     st = self.stream() if st is None else st
-    assert x.shape == (B,) + self.in_shape and x.is_contiguous()
+    assert x.shape == (self.B,) + self.in_shape and x.is_contiguous()
     self.x = x
     self._clear_stale_act_words(st)
+    self._latent_fwd(x, eps, st, self.neck, self.lat_block, for_step=False)
+    # (the quantiser: -> (codes, z_q), both [B, H]; vq_idx holds the assignments)
+    return (self.enc.outs[-1] if self.vq_K is not None else self.p), self.z
+
+  def _latent_fwd(self, x, eps, st, neck: bool, block: bool, for_step: bool):
+    """x -> encoder -> the latent (p, z, kl; the quantiser: z = z_q, vq_idx) by ONE of four paths; -> (the decoder's
+    input, the first decoder layer still to run).  `for_step` False (run_encoder): a forward-only call -- the quantiser
+    counts no code usage, the neck stops behind the latent block and leaves the decoder's activation word alone; the
+    decoder layers the fused launches evaluate as well land in dec.outs[0 / 1], unused."""
+    lib, B, D = self.lib, self.B, self.D
     if self.vq_K is not None:
-      # -> (codes, z_q), both [B, H]; vq_idx holds the assignments (a forward-only call of the quantiser)
-      h_e = self.enc.forward(x, st)
-      self._vq_assign(h_e, st, count=False)
-      return h_e, self.z
-    lw = self.params[self.lat_w_off:]
-    lb = self.params[self.lat_b_off:]
-    if self.neck:
-      # conv3 .. deconv1 as ONE launch (neck.hip; the decoder's first two layers it also evaluates land in dec.outs[0 / 1],
-      # unused here -- and without touching the decoder's activation word)
-      if eps is not None and eps is not self.eps:
-        self.eps.copy_(eps)
+      self._vq_assign(self.enc.forward(x, st), st, count=for_step)
+      return self.z, 0
+    if eps is not None and eps is not self.eps:
+      self.eps.copy_(eps)
+    lw, lb = self.params[self.lat_w_off:], self.params[self.lat_b_off:]
+    cap = self.hp(H_CAP) if self.capacity_on else None
+    if neck:
+      # conv3 .. deconv1 as ONE launch (neck.hip)
       self.enc.forward(x, st, upto=len(self.enc_recs) - 2)
-      self._neck_fwd(eps, st, y1_word=False, enc_only=True)
-      return self.p, self.z
-    if self.lat_block:
-      # noise + projection + reparameterisation + KL as ONE launch (latent_block.hip; the decoder's first Dense it
-      # also evaluates lands in dec.outs[0], unused here): three launches less than the separate kernels
-      if eps is not None and eps is not self.eps:
-        self.eps.copy_(eps)
+      self._neck_fwd(eps, st, y1_word=for_step, enc_only=not for_step)
+      return self.dec.outs[1], 2
+    if block:
+      # noise + projection + reparameterisation + KL + the decoder's first Dense as ONE launch (latent_block.hip): three
+      # launches less than the separate kernels
       h_e = self.enc.forward(x, st)
       r0 = self.dec_recs[0]
       lib.odin_latent_block_fwd(h_e.data_ptr(), lw.data_ptr(), lb.data_ptr(),
@@ -1484,20 +1542,17 @@ class VAEEngine:
                                 self.seed, self.hp(N_HYPER), self.p.data_ptr(), self.z.data_ptr(),
                                 self.kl.data_ptr(), self.fbmask.data_ptr(), self.dec.w(0).data_ptr(),
                                 self.dec.b(0).data_ptr(), self.dec.outs[0].data_ptr(), B, self.hdim, D,
-                                r0.N, ACT[r0.act], int(self.analytic), self.free_bits,
-                                self.hp(H_CAP) if self.capacity_on else None, st)
-      return self.p, self.z
+                                r0.N, ACT[r0.act], int(self.analytic), self.free_bits, cap, st)
+      return self.dec.outs[0], 1
     if eps is None:
       lib.odin_rng_normal(self.eps.data_ptr(), B * D, self.seed, self.hp(N_HYPER), st)
-    elif eps is not self.eps:
-      self.eps.copy_(eps)
     h_e = self.enc.forward(x, st)
     lib.odin_dense_fwd(h_e.data_ptr(), lw.data_ptr(), lb.data_ptr(), self.p.data_ptr(), B,
                        self.hdim, 2 * D, 0, st)
     lib.odin_latent_fwd(self.p.data_ptr(), self.eps.data_ptr(), self.z.data_ptr(),
                         self.kl.data_ptr(), self.fbmask.data_ptr(), B, D, int(self.analytic),
-                        self.free_bits, self.hp(H_CAP) if self.capacity_on else None, st)
-    return self.p, self.z
+                        self.free_bits, cap, st)
+    return self.z, 0
 
   def run_decoder(self, z: torch.Tensor, st=None):
     st = self.stream() if st is None else st
@@ -1514,27 +1569,28 @@ class VAEEngine:
   def observation_llk(self, h_d: torch.Tensor, x: torch.Tensor, out: torch.Tensor, st=None):
     """out[b] = log p(x_b | decoder output h_d_b) through the fused observation kernel (its
     gradient output lands in the decoder's gradient buffer and is ignored)."""
-    lib, B = self.lib, self.B
     st = self.stream() if st is None else st
-    npart = C.c_int(0)
-    gl = self.dec.gouts[-1]
-    if self.observation == 'bernoulli':
-      lib.odin_elbo_bernoulli_fwd_bwd(h_d.data_ptr(), x.data_ptr(), self.llk_part.data_ptr(),
-                                      gl.data_ptr(), self.hp(H_INVB), B, self.n_per,
-                                      C.byref(npart), st)
-    elif self.observation == 'mixqlogistic':
-      Cc = self.in_shape[-1]
-      lib.odin_elbo_mixqlogistic_fwd_bwd(h_d.data_ptr(), x.data_ptr(), self.llk_part.data_ptr(),
-                                         gl.data_ptr(), self.hp(H_INVB), B, self.n_per // Cc, Cc,
-                                         MIXQL_K, C.byref(npart), st)
-    else:
-      Cc = self.in_shape[-1]
-      lib.odin_elbo_gaussian_fwd_bwd(h_d.data_ptr(), x.data_ptr(), self.llk_part.data_ptr(),
-                                     gl.data_ptr(), self.hp(H_INVB), B, self.n_per // Cc, Cc,
-                                     OBS_MODE[self.observation],
-                                     C.byref(npart), st)
-    lib.odin_sum_parts(self.llk_part.data_ptr(), npart.value, out.data_ptr(), B, st)
+    npart = self._observation_fwd_bwd(h_d.data_ptr(), x.data_ptr(), self.llk_part.data_ptr(),
+                                      self.dec.gouts[-1].data_ptr(), None, st)
+    self.lib.odin_sum_parts(self.llk_part.data_ptr(), npart, out.data_ptr(), self.B, st)
     return out
+
+  def _observation_fwd_bwd(self, h_d, x, part, dlogits, top_word, st) -> int:
+    """the stand-alone kernel of self.observation on device addresses: per-sample partial log-likelihoods of x under
+    the decoder output h_d -> part, the top gradient -> dlogits (Bernoulli: max |dlogits| folded into `top_word` where
+    one is given); every address None: the dry run.  -> the partials per sample"""
+    lib, B, Cc = self.lib, self.B, self.in_shape[-1]
+    inv_b = None if h_d is None else self.hp(H_INVB)
+    npart = C.c_int(0)
+    if self.observation == 'bernoulli':
+      lib.odin_elbo_bernoulli_fwd_bwd_ranged(h_d, x, part, dlogits, inv_b, B, self.n_per, C.byref(npart), top_word, st)
+    elif self.observation == 'mixqlogistic':
+      lib.odin_elbo_mixqlogistic_fwd_bwd(h_d, x, part, dlogits, inv_b, B, self.n_per // Cc, Cc, MIXQL_K,
+                                         C.byref(npart), st)
+    else:
+      lib.odin_elbo_gaussian_fwd_bwd(h_d, x, part, dlogits, inv_b, B, self.n_per // Cc, Cc,
+                                     OBS_MODE[self.observation], C.byref(npart), st)
+    return npart.value
 
   # ---- forward -----------------------------------------------------------------------
   def forward(self, x: torch.Tensor, eps: Optional[torch.Tensor] = None, st=None,
@@ -1544,7 +1600,7 @@ class VAEEngine:
     noise on device from the Philox stream (seed, step); `prior` [M, D] (latent_reg='mmd'): an explicit prior sample
     instead of the one drawn from (prior_seed, step).  `after_latent()` (optional) is called once z is issued
     on the stream -- FactorVAE forks its discriminator pass onto a side stream there, beside the decoder."""
-    lib, B, D = self.lib, self.B, self.D
+    lib, B = self.lib, self.B
     st = self.stream() if st is None else st
     assert x.shape == (B,) + self.in_shape and x.is_contiguous()
     self.x = x
@@ -1554,8 +1610,6 @@ class VAEEngine:
         self.reg_y.copy_(prior.reshape(self.reg_y.shape))
     else:
       assert prior is None, 'an explicit prior sample needs latent_reg="mmd"'
-    lw = self.params[self.lat_w_off:]
-    lb = self.params[self.lat_b_off:]
     self._used_block = self.lat_block and fused
     self._used_neck = self.neck and fused
     if self.vamp_K is not None:
@@ -1564,41 +1618,7 @@ class VAEEngine:
     # (outs[0] of the decoder comes from the bottleneck launch in the fused step: no word for layer 1's input then)
     if len(self.dec_recs) > 1:
       self.dec.set_x_word(1, not self._used_block)
-    if self._used_neck:
-      if eps is not None and eps is not self.eps:
-        self.eps.copy_(eps)
-      self.enc.forward(x, st, upto=len(self.enc_recs) - 2)
-      self._neck_fwd(eps, st)
-      dec_in, dec_start = self.dec.outs[1], 2
-    elif self._used_block:
-      if eps is not None and eps is not self.eps:
-        self.eps.copy_(eps)
-      h_e = self.enc.forward(x, st)
-      r0 = self.dec_recs[0]
-      lib.odin_latent_block_fwd(h_e.data_ptr(), lw.data_ptr(), lb.data_ptr(),
-                                None if eps is None else self.eps.data_ptr(), self.eps.data_ptr(),
-                                self.seed, self.hp(N_HYPER), self.p.data_ptr(), self.z.data_ptr(),
-                                self.kl.data_ptr(), self.fbmask.data_ptr(), self.dec.w(0).data_ptr(),
-                                self.dec.b(0).data_ptr(), self.dec.outs[0].data_ptr(), B, self.hdim, D,
-                                r0.N, ACT[r0.act], int(self.analytic), self.free_bits,
-                                self.hp(H_CAP) if self.capacity_on else None, st)
-      dec_in, dec_start = self.dec.outs[0], 1
-    elif self.vq_K is not None:
-      h_e = self.enc.forward(x, st)
-      self._vq_assign(h_e, st)
-      dec_in, dec_start = self.z, 0
-    else:
-      if eps is None:
-        lib.odin_rng_normal(self.eps.data_ptr(), B * D, self.seed, self.hp(N_HYPER), st)
-      elif eps is not self.eps:
-        self.eps.copy_(eps)
-      h_e = self.enc.forward(x, st)
-      lib.odin_dense_fwd(h_e.data_ptr(), lw.data_ptr(), lb.data_ptr(), self.p.data_ptr(), B,
-                         self.hdim, 2 * D, 0, st)
-      lib.odin_latent_fwd(self.p.data_ptr(), self.eps.data_ptr(), self.z.data_ptr(),
-                          self.kl.data_ptr(), self.fbmask.data_ptr(), B, D, int(self.analytic),
-                          self.free_bits, self.hp(H_CAP) if self.capacity_on else None, st)
-      dec_in, dec_start = self.z, 0
+    dec_in, dec_start = self._latent_fwd(x, eps, st, self._used_neck, self._used_block, for_step=True)
     if after_latent is not None:
       after_latent()
     npart = C.c_int(0)
@@ -1657,26 +1677,11 @@ class VAEEngine:
       self._used_fused = False
       llk_part = self.llk_part
       h_d = self.dec.forward(dec_in, st, start=dec_start)
-    gl = self.dec.gouts[-1]
-    if self._used_fused or self._used_head:
-      pass
-    elif self.observation == 'bernoulli':
-      lib.odin_elbo_bernoulli_fwd_bwd_ranged(h_d.data_ptr(), x.data_ptr(), self.llk_part.data_ptr(),
-                                             gl.data_ptr(), self.hp(H_INVB), B, self.n_per, C.byref(npart),
-                                             self.dec.dy_word[-1] if self._bern_keeps_top else None, st)
-    elif self.observation == 'mixqlogistic':
-      Cc = self.in_shape[-1]
-      lib.odin_elbo_mixqlogistic_fwd_bwd(h_d.data_ptr(), x.data_ptr(), self.llk_part.data_ptr(),
-                                         gl.data_ptr(), self.hp(H_INVB), B, self.n_per // Cc, Cc,
-                                         MIXQL_K, C.byref(npart), st)
-    else:
-      Cc = self.in_shape[-1]
-      lib.odin_elbo_gaussian_fwd_bwd(h_d.data_ptr(), x.data_ptr(), self.llk_part.data_ptr(),
-                                     gl.data_ptr(), self.hp(H_INVB), B, self.n_per // Cc, Cc,
-                                     OBS_MODE[self.observation],
-                                     C.byref(npart), st)
+    if not (self._used_fused or self._used_head):
+      npart.value = self._observation_fwd_bwd(h_d.data_ptr(), x.data_ptr(), self.llk_part.data_ptr(),
+                                              self.dec.gouts[-1].data_ptr(),
+                                              self.dec.dy_word[-1] if self._bern_keeps_top else None, st)
     self.n_part = npart.value
-    tcp = None
     if self.tc_sharded and tc_split:
       # segmented step: only the local part here; the caller runs tc_gather | tc_shard | tc_scatter and
       # then finalize(tc_ptr) (train_step's program)
@@ -1689,49 +1694,13 @@ class VAEEngine:
         self._dip_moments(st)
       self._llk_part_used = llk_part
       return h_d
-    if self.tc_sharded:
-      self._tc_pack()
-      self._tc_gather()
-      self._tc_shard(st)
-      self._tc_scatter()
-      tcp = self.tc_ws.data_ptr()
-    elif self.tc_mode == 'betatc':
-      lib.odin_total_correlation_fwd_bwd(self.z.data_ptr(), self.p.data_ptr(),
-                                         self.tc_ws.data_ptr(), self.tc_dz.data_ptr(),
-                                         self.tc_dloc.data_ptr(), self.tc_dscale.data_ptr(),
-                                         self.hp(H_TCGRAD), B, D, st)
-      tcp = self.tc_ws.data_ptr()
-    elif self.reg_sharded:
-      if self.reg_mode != 'mmd':
-        self._dip_moments(st)
-      for kind, fn in self._reg_segments():
-        fn()
-      tcp = self.reg_ws.data_ptr()
-    elif self.reg_mode == 'mmd':
-      lib.odin_mmd_fwd_bwd(self.z.data_ptr(), self._prior_ptr(), self.reg_ws.data_ptr(), self.reg_dz.data_ptr(),
-                           None, self.hp(H_TCGRAD), B, self.mmd_M, D, self.mmd_kernel, self.prior_key,
-                           self.hp(N_HYPER), st)
-      tcp = self.reg_ws.data_ptr()
-    elif self.reg_mode is not None:
-      lib.odin_dip_fwd_bwd(self.p.data_ptr(), self.reg_ws.data_ptr(), self.reg_dloc.data_ptr(),
-                           self.reg_dscale.data_ptr() if self.dip_type2 else None, None, self.hp(H_TCGRAD), B, D,
-                           self.dip_type2, self.dip_lambda[0], self.dip_lambda[1], st)
-      tcp = self.reg_ws.data_ptr()
-    elif self.vamp_K is not None:
-      # (the value unscaled: the finalisation multiplies it by H_TCCOEF = beta, once)
-      lib.odin_vamprior_fwd_bwd(self.z.data_ptr(), self.vamp_pu.data_ptr(), self.vamp_ws.data_ptr(),
-                                self.vamp_c.data_ptr(), self.vamp_dz.data_ptr(), self.vamp_dpu.data_ptr(), None,
-                                self.hp(H_TCGRAD), B, self.vamp_K, D, st)
-      tcp = self.vamp_ws.data_ptr()
-    elif self.vq_K is not None:
-      tcp = self.out8[4:].data_ptr()   # m, left by the quantiser; the finalisation multiplies it by H_TCCOEF
+    if self._term.launch is not None:
+      self._term.launch(st)
     self._llk_part_used = llk_part
-    if tc_ptr is not None:
-      tcp = tc_ptr
     if finalize:
-      lib.odin_elbo_finalize(llk_part.data_ptr(), self.n_part, self.kl.data_ptr(),
-                             self.hp(H_BETA), tcp, self.llk.data_ptr(), self.out4.data_ptr(), B,
-                             st)
+      lib.odin_elbo_finalize(llk_part.data_ptr(), self.n_part, self.kl.data_ptr(), self.hp(H_BETA),
+                             self._term.ptr() if tc_ptr is None else tc_ptr, self.llk.data_ptr(), self.out4.data_ptr(),
+                             B, st)
     return h_d
 
   # total_correlation over the GLOBAL batch (losses.py:136-157 couples all pairs): one all-gather of
@@ -1830,25 +1799,26 @@ class VAEEngine:
     """phase None: the whole backward pass and ONE slab reduction.  'dec' / 'enc': the decoder's share
     (down to dz) / the rest, each followed by the reduction of its own slabs -- the two-bucket
     data-parallel step all-reduces the decoder's gradients while 'enc' runs."""
-    lib, B, D = self.lib, self.B, self.D
+    lib = self.lib
     st = self.stream() if st is None else st
+    if phase == 'dec':
+      jobs, _, _ = self._backward_dec(st, None)
+      arr = (ReduceJob * len(jobs))(*jobs)
+      self._jobs_keepalive0 = arr
+      lib.odin_slab_reduce(arr, len(jobs), st)
+      return
     fork, join = self._fork() if phase is None else (None, (lambda: None))
     if phase is None and fork is None and self.defer_wgrad:
       # the plane layers' weight gradients depend on nothing but their own layer's tensors: collected here and issued
       # as ONE launch just before the slab reduction (include/odin_hip.h: odin_wgrad_planes_defer_begin)
       lib.odin_wgrad_planes_defer_begin()
-    if phase == 'enc':
-      jobs = []
-      late_jobs = []
-      early = False
-    else:
-      jobs, late_jobs, early = self._backward_dec(st, fork)
-      if phase == 'dec':
-        arr = (ReduceJob * len(jobs))(*jobs)
-        self._jobs_keepalive0 = arr
-        lib.odin_slab_reduce(arr, len(jobs), st)
-        return
-    self._backward_enc(st, extra_dz, fork, join, jobs, late_jobs, early)
+    try:
+      jobs, late_jobs, early = ([], [], False) if phase == 'enc' else self._backward_dec(st, fork)
+      self._backward_enc(st, extra_dz, fork, jobs, late_jobs)
+      join()
+    finally:
+      lib.odin_wgrad_planes_defer_end(st)   # (no-op unless a collection is open; a failed launch must not leave one)
+    self._reduce_slabs(jobs, early, st)
 
   def _backward_dec(self, st, fork):
     lib, B, D = self.lib, self.B, self.D
@@ -1861,23 +1831,19 @@ class VAEEngine:
       jobs = self.dec.backward(self.z, self.dec.gouts[-2], st, dx_out=self.dz, last=nd - 2,
                                skip_bias_of_last=True, fork=fork,
                                side_jobs=late_jobs if early else None, first=self._dec_first())
-      ts, stride = self.tail_slab, self.tail_slab.shape[1]
+      ts = self.tail_slab
       # (dW1 | db1) of the 1x1 conv, then the bias gradient of the fused layer
-      jobs.append(ReduceJob(ts.data_ptr(), self.grads[b.w_off:].data_ptr(), co * c1 + c1,
-                            self.tail_rows, stride, 0))
+      jobs.append(self._slab_job(ts, b.w_off, self.tail_rows, n=co * c1 + c1))
       jobs.append(ReduceJob(ts[:, co * c1 + c1:].data_ptr(), self.grads[a.b_off:].data_ptr(), co,
-                            self.tail_rows, stride, 0))
+                            self.tail_rows, ts.shape[1], 0))
     elif self._used_head:
       nd = len(self.dec_recs)
       a, b = self.dec_recs[-2], self.dec_recs[-1]
       jobs = self.dec.backward(self.z, self.dec.gouts[-2], st, dx_out=self.dz, last=nd - 2, fork=fork,
                                side_jobs=late_jobs if early else None, first=self._dec_first())
-      hs = self.head_slab
-      jobs.append(ReduceJob(hs.data_ptr(), self.grads[b.w_off:].data_ptr(), hs.shape[1], self.head_rows,
-                            hs.shape[1], 0))  # (dW1 | db1) of the 1x1 head
+      jobs.append(self._slab_job(self.head_slab, b.w_off, self.head_rows))  # (dW1 | db1) of the 1x1 head
       if self.head_colsum is not None:  # bias gradient of the Conv2DTranspose below = column sums of gouts[-2]
-        hc = self.head_colsum
-        jobs.append(ReduceJob(hc.data_ptr(), self.grads[a.b_off:].data_ptr(), a.b_n, self.head_rows, hc.shape[1], 0))
+        jobs.append(self._slab_job(self.head_colsum, a.b_off, self.head_rows, n=a.b_n))
     else:
       jobs = self.dec.backward(self.z, self.dec.gouts[-1], st, dx_out=self.dz, fork=fork,
                                side_jobs=late_jobs if early else None, first=self._dec_first())
@@ -1890,29 +1856,18 @@ class VAEEngine:
       jobs = []
     return jobs, late_jobs, early
 
-  def _backward_enc(self, st, extra_dz, fork, join, jobs, late_jobs, early):
+  def _backward_enc(self, st, extra_dz, fork, jobs, late_jobs):
     lib, B, D = self.lib, self.B, self.D
-    dzx = extra_dz.data_ptr() if extra_dz is not None else None
-    if self.tc_mode == 'betatc':
-      assert extra_dz is None
-      dzx = self.tc_dz.data_ptr()
-    tl = self.tc_dloc.data_ptr() if self.tc_mode == 'betatc' else None
-    ts = self.tc_dscale.data_ptr() if self.tc_mode == 'betatc' else None
-    if self.reg_mode == 'mmd':
-      assert extra_dz is None
-      dzx = self.reg_dz.data_ptr()
-    elif self.reg_mode is not None:
-      tl = self.reg_dloc.data_ptr()
-      ts = self.reg_dscale.data_ptr() if self.dip_type2 else None
-    if self.vamp_K is not None:
-      assert extra_dz is None
-      dzx = self.vamp_dz.data_ptr()
+    T = self._term
+    # (the caller's dz -- FactorVAE's -- and the term's share one input of the latent backward; the quantiser has none)
+    assert extra_dz is None or (T.dz is None and self.vq_K is None)
+    dzx, tl, ts = (None if t is None else t.data_ptr()
+                   for t in (T.dz if extra_dz is None else extra_dz, T.dloc, T.dscale))
     h_e = self.enc.outs[-1]
     last = self.enc_recs[-1]
     aux_act = ACT[last.act]
     lw = self.params[self.lat_w_off:]
     if self.vq_K is not None:
-      assert extra_dz is None
       self._vq_bwd(st, jobs)
     elif self._bwd_neck():
       ne = len(self.enc_recs)
@@ -1926,10 +1881,8 @@ class VAEEngine:
                                 self.dz.data_ptr(), self.dp.data_ptr(), self.enc.gouts[-1].data_ptr(),
                                 self.lb_slab0.data_ptr(), self.lb_slabl.data_ptr(), B, self.hdim, D, r0.N,
                                 int(self.analytic), self.enc.set_top_word(True), st)
-      jobs.append(ReduceJob(self.lb_slab0.data_ptr(), self.grads[r0.w_off:].data_ptr(),
-                            self.lb_slab0.shape[1], self.lb_rows, self.lb_slab0.shape[1], 0))
-      jobs.append(ReduceJob(self.lb_slabl.data_ptr(), self.grads[self.lat_w_off:].data_ptr(),
-                            self.lb_slabl.shape[1], self.lb_rows, self.lb_slabl.shape[1], 0))
+      jobs.append(self._slab_job(self.lb_slab0, r0.w_off, self.lb_rows))
+      jobs.append(self._slab_job(self.lb_slabl, self.lat_w_off, self.lb_rows))
     else:
       lib.odin_latent_bwd(self.p.data_ptr(), self.eps.data_ptr(), self.z.data_ptr(),
                           self.dz.data_ptr(), dzx, self.fbmask.data_ptr(), self.hp(H_KLW), tl, ts,
@@ -1938,8 +1891,7 @@ class VAEEngine:
       lib.odin_dense_wgrad(h_e.data_ptr(), self.dp.data_ptr(), self.lat_slab.data_ptr(),
                            C.byref(rows), B, self.hdim, 2 * D,
                            st if (fork is None or not fork.wants(True)) else fork(-1))  # small
-      jobs.append(ReduceJob(self.lat_slab.data_ptr(), self.grads[self.lat_w_off:].data_ptr(),
-                            self.lat_slab.shape[1], rows.value, self.lat_slab.shape[1], 0))
+      jobs.append(self._slab_job(self.lat_slab, self.lat_w_off, rows.value))
       auxp = h_e.data_ptr() if aux_act != 0 else None
       bslab = self.enc.bslabs[-1]
       # (the projection's data gradient keeps the range word of the encoder's top gradient where its kernel family does)
@@ -1948,8 +1900,7 @@ class VAEEngine:
                          bslab.data_ptr() if bslab is not None else None, C.byref(rows), None, None, B,
                          self.hdim, 2 * D, 0, 1, None, top, st)
       if bslab is not None:
-        jobs.append(ReduceJob(bslab.data_ptr(), self.grads[last.b_off:].data_ptr(), last.b_n,
-                              rows.value, last.b_n, 0))
+        jobs.append(self._slab_job(bslab, last.b_off, rows.value))
     if not self._bwd_neck():
       jobs += self.enc.backward(self.x, self.enc.gouts[-1], st, fork=fork)
     if self.vamp_K is not None:
@@ -1961,10 +1912,12 @@ class VAEEngine:
     rw = self.range_words
     jobs.append(ReduceJob(rw.data_ptr(), rw.data_ptr(), rw.numel(), 0, rw.numel(), 0))
     self._act_words_dirty = False
-    join()
+
+  def _reduce_slabs(self, jobs, early, st):
+    """the step's last backward launch: every slab job of the pass (with the gradient norm's stage 1 where it rides)"""
+    lib = self.lib
     arr = (ReduceJob * len(jobs))(*jobs)
     self._jobs_keepalive = arr
-    lib.odin_wgrad_planes_defer_end(st)   # (no-op unless backward() opened a collection)
     if callable(self.debug_check_ranges):
       self.debug_check_ranges(self)   # (a caller's audit of every word, on the same words: tests/range_audit.py)
     elif self.debug_check_ranges:
@@ -2122,21 +2075,17 @@ class VAEEngine:
       P.append(('c', self._tc_gather))
       P.append(('k', self._tc_shard))
       P.append(('c', self._tc_scatter))
-      P.append(('k', lambda: self.finalize(self.tc_ws.data_ptr())))
+      P.append(('k', lambda: self.finalize(self._term.ptr())))
     elif self.reg_sharded:
       P.append(('k', lambda: self.forward(x, eps, tc_split=True, prior=prior)))
       P += self._reg_segments()
-      P.append(('k', lambda: self.finalize(self.reg_ws.data_ptr())))
+      P.append(('k', lambda: self.finalize(self._term.ptr())))
     else:
       # the ELBO finalisation (llk[B], loss, mean terms: nothing in the backward pass reads them) rides in the
       # update's first launch instead of being a launch of its own
       def fwd():
         self.forward(x, eps, finalize=False, prior=prior)
-        tcp = (self.tc_ws.data_ptr() if self.tc_mode == 'betatc' else
-               self.reg_ws.data_ptr() if self.reg_mode is not None else
-               self.vamp_ws.data_ptr() if self.vamp_K is not None else
-               self.out8[4:].data_ptr() if self.vq_K is not None else None)
-        self._fin_pending = (self._llk_part_used.data_ptr(), self.n_part, tcp)
+        self._fin_pending = (self._llk_part_used.data_ptr(), self.n_part, self._term.ptr())
       P.append(('k', fwd))
     if self.is_dp and self.dp_buckets >= 2:
       cur = lambda: torch.cuda.current_stream(self.device)

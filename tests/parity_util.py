@@ -2,6 +2,7 @@
 import numpy as np
 import torch
 
+from odin_ai_amd import _lib
 from oracle import vae_oracle as vo
 
 
@@ -104,3 +105,22 @@ def check_engine_vs_oracle(eng, model: vo.OracleVAE, P, x, eps, beta, lr=1e-3, t
     # continue from the oracle's parameters so that errors do not compound in the check
   report['param_unmasked_max'] = report_unmasked
   return report
+
+
+def oracle_params(vae):
+  return {k: v.detach().cpu().numpy(force=True).astype(np.float64) for k, v in vae.trainable_variables.items()}
+
+
+def reduce_slab(bk, slab, rows, n):
+  L = bk.L
+  out = bk.zeros(n)
+  job = (_lib.ReduceJob * 1)(_lib.ReduceJob(slab.data_ptr(), out.data_ptr(), n, rows, slab.shape[1], 0))
+  L.odin_slab_reduce(job, 1, None)
+  return out.cpu().numpy()
+
+
+def close(a, b, tol=2e-5):
+  a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
+  err = np.abs(a - b).max()
+  ref = max(1.0, np.abs(b).max())
+  assert err <= tol * ref, (err, ref)

@@ -19,6 +19,7 @@ and it records what VAEEngine._jobs_cover returned (`cover`).
 """
 from typing import Dict, List, Optional, Tuple
 
+import numpy as np
 import torch
 
 from odin_ai_amd.engine import RANGE_WORDS
@@ -147,3 +148,11 @@ class RangeAudit:
 
   def n_checked(self) -> int:
     return sum(len(s) for s in self.steps)
+
+
+def bern_targets(shape, seed=3):
+  """Bernoulli targets outside [0, 1], every fifth exactly 0 and every fifth exactly 1"""
+  x = np.random.default_rng(seed).uniform(-2.0, 6.0, size=shape)
+  x.reshape(-1)[::5] = 0.0
+  x.reshape(-1)[1::5] = 1.0
+  return x

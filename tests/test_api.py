@@ -10,6 +10,8 @@ from odin_ai_amd.networks import RVconf, SequentialNetwork, get_networks
 from odin_ai_amd.vae import (AnnealingVAE, BetaCapacityVAE, BetaTCVAE, BetaVAE, FactorVAE,
                              VariationalAutoencoder, get_vae)
 from oracle import vae_oracle as vo
+from tests.engine_util import factor_batch, tiny_batch, tiny_nets
+from tests.parity_util import oracle_params
 
 
 @pytest.fixture(scope='module')
@@ -22,28 +24,11 @@ def DEV(bk):
   return bk.dev
 
 
-def tiny_nets(C=1, zdim=4, hw=8):
-  enc = [('center',), ('conv', 8, 4, 2, 'elu'), ('conv', 16, 4, 2, 'elu'), ('flatten',),
-         ('dense', 24, 'linear')]
-  dec = [('dense', 32, 'linear'), ('reshape', (2, 2, 8)), ('deconv', 16, 4, 2, 'elu'),
-         ('deconv', 8, 4, 2, 'elu'), ('conv', C, 1, 1, 'linear')]
-  return dict(encoder=SequentialNetwork(enc, 'Encoder', (hw, hw, C)),
-              decoder=SequentialNetwork(dec, 'Decoder', (zdim,)),
-              observation=RVconf((hw, hw, C), 'bernoulli', projection=False, name='image'),
-              latents=RVconf((zdim,), 'mvndiag', projection=True, name='latents'))
-
-
-def oracle_params(vae):
-  return {k: v.detach().cpu().numpy(force=True).astype(np.float64) for k, v in vae.trainable_variables.items()}
-
-
 def test_api_call_elbo_and_optimize(L, DEV):
   nets = tiny_nets()
   vae = BetaVAE(beta=4.0, device=DEV, lib=L, **nets)
   B = 6
-  rng = np.random.default_rng(0)
-  x = np.clip(rng.random((B, 8, 8, 1)), 1e-6, 1 - 1e-6).astype(np.float32)
-  eps = rng.standard_normal((B, 4)).astype(np.float32)
+  x, eps = tiny_batch(0, B)
   px, qz = vae(x, eps=eps)
   assert px.mean().shape == (B, 8, 8, 1) and qz.mean().shape == (B, 4)
   assert qz.event_shape == (4,) and px.batch_shape == (B,)
@@ -103,9 +88,7 @@ def test_annealing_and_betatc(L, DEV):
   nets = tiny_nets()
   tcv = BetaTCVAE(beta=3.0, device=DEV, lib=L, **nets)
   B = 6
-  rng = np.random.default_rng(2)
-  x = np.clip(rng.random((B, 8, 8, 1)), 1e-6, 1 - 1e-6).astype(np.float32)
-  eps = rng.standard_normal((B, 4)).astype(np.float32)
+  x, eps = tiny_batch(2, B)
   llk, kl = tcv.elbo_components(x, eps=eps)
   assert set(kl) == {'kl_latents', 'tc_latents'}
   model = vo.OracleVAE(nets['encoder'].layers, nets['decoder'].layers, (8, 8, 1), 4, beta=3.0,
@@ -119,10 +102,7 @@ def test_factor_vae_two_steps_match_oracle(L, DEV):
   nets = tiny_nets()
   B1, D = 4, 4
   fv = FactorVAE(discriminator_units=(16, 16), tc_coef=7.0, device=DEV, lib=L, **nets)
-  rng = np.random.default_rng(3)
-  x = np.clip(rng.random((2 * B1, 8, 8, 1)), 1e-6, 1 - 1e-6).astype(np.float32)
-  eps, eps2 = (rng.standard_normal((B1, D)).astype(np.float32) for _ in range(2))
-  perm = np.stack([rng.permutation(B1) for _ in range(D)], 1).astype(np.int32)
+  x, eps, eps2, perm = factor_batch(3)
   P = oracle_params(fv)
   disc = fv._discriminator(B1)
   DP = {(k[1], k[2]): v.detach().numpy(force=True).astype(np.float64)
@@ -159,10 +139,7 @@ def test_factor_vae_iteration_gradients_and_both_adams(L, DEV, units):
   nets = tiny_nets()
   B1, D = 4, 4
   fv = FactorVAE(discriminator_units=units, tc_coef=7.0, device=DEV, lib=L, **nets)
-  rng = np.random.default_rng(11)
-  x = np.clip(rng.random((2 * B1, 8, 8, 1)), 1e-6, 1 - 1e-6).astype(np.float32)
-  eps, eps2 = (rng.standard_normal((B1, D)).astype(np.float32) for _ in range(2))
-  perm = np.stack([rng.permutation(B1) for _ in range(D)], 1).astype(np.int32)
+  x, eps, eps2, perm = factor_batch(11)
   rep = check_factor_vae_iteration(fv, nets, units, B1, x, eps, eps2, perm, clip=100.0)
   assert fv.step == 1000
 
@@ -174,9 +151,7 @@ def test_beta_capacity_vae_matches_oracle(L, DEV):
   from odin_ai_amd.interpolation import linear
   nets = tiny_nets()
   B, D = 6, 4
-  rng = np.random.default_rng(5)
-  x = np.clip(rng.random((B, 8, 8, 1)), 1e-6, 1 - 1e-6).astype(np.float32)
-  eps = rng.standard_normal((B, D)).astype(np.float32)
+  x, eps = tiny_batch(5, B)
   for start_step, c_max in ((0, 0.02), (7, 400.0), (3, 3.0)):  # kl > C everywhere, kl < C everywhere, mixed
     vae = BetaCapacityVAE(gamma=10.0, c_min=0.01, c_max=c_max, n_steps=10, analytic=True, device=DEV, lib=L,
                           **nets)
@@ -256,10 +231,7 @@ def test_factor_vae_torch_autograd_cross_check(L, DEV):
   nets = tiny_nets()
   B1, D, units = 4, 4, (16, 16)
   fv = FactorVAE(discriminator_units=units, tc_coef=7.0, device=DEV, lib=L, **nets)
-  rng = np.random.default_rng(12)
-  x = np.clip(rng.random((2 * B1, 8, 8, 1)), 1e-6, 1 - 1e-6).astype(np.float32)
-  eps, eps2 = (rng.standard_normal((B1, D)).astype(np.float32) for _ in range(2))
-  perm = np.stack([rng.permutation(B1) for _ in range(D)], 1).astype(np.int32)
+  x, eps, eps2, perm = factor_batch(12)
   check_factor_vae_full_size(fv, nets, units, B1, x, eps, eps2, perm, clip=100.0)
 
 
@@ -275,9 +247,7 @@ def test_optimize_gradient_policies_match_oracle(L, DEV, kw):
   nets = tiny_nets()
   vae = BetaVAE(beta=2.0, device=DEV, lib=L, **nets)
   B = 6
-  rng = np.random.default_rng(4)
-  x = np.clip(rng.random((B, 8, 8, 1)), 1e-6, 1 - 1e-6).astype(np.float32)
-  eps = rng.standard_normal((B, 4)).astype(np.float32)
+  x, eps = tiny_batch(4, B)
   model = vo.OracleVAE(nets['encoder'].layers, nets['decoder'].layers, (8, 8, 1), 4, beta=2.0)
   P = oracle_params(vae)
   f = model.forward(P, x.astype(np.float64), eps.astype(np.float64))
@@ -470,9 +440,7 @@ def test_mixture_quantized_logistic_model(L, DEV, C):
                                kwargs=dict(n_components=10))
   vae = BetaVAE(beta=2.0, device=DEV, lib=L, **nets)
   B = 6
-  rng = np.random.default_rng(5)
-  x = np.clip(rng.random((B, 8, 8, C)), 1e-6, 1 - 1e-6).astype(np.float32)
-  eps = rng.standard_normal((B, 4)).astype(np.float32)
+  x, eps = tiny_batch(5, B, C=C)
   model = vo.OracleVAE(nets['encoder'].layers, nets['decoder'].layers, (8, 8, C), 4, beta=2.0,
                        observation='mixqlogistic')
   P = oracle_params(vae)

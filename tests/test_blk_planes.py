@@ -12,21 +12,7 @@ import torch
 
 from odin_ai_amd import _lib
 from oracle import vae_oracle as vo
-
-
-def reduce_slab(bk, slab, rows, n):
-  L = bk.L
-  out = bk.zeros(n)
-  job = (_lib.ReduceJob * 1)(_lib.ReduceJob(slab.data_ptr(), out.data_ptr(), n, rows, slab.shape[1], 0))
-  L.odin_slab_reduce(job, 1, None)
-  return out.cpu().numpy()
-
-
-def close(a, b, tol=2e-5):
-  a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-  err = np.abs(a - b).max()
-  ref = max(1.0, np.abs(b).max())
-  assert err <= tol * ref, (err, ref)
+from tests.parity_util import close, reduce_slab
 
 
 @pytest.fixture

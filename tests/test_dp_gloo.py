@@ -2,47 +2,25 @@
 full batch.  Covers the flat-bucket all-reduce, the 1/B_global loss scaling and the
 replicated Adam step of `VAEEngine`."""
 import os
-import socket
 import sys
 
 import numpy as np
 import pytest
 import torch
 import torch.distributed as dist
-import torch.multiprocessing as mp
+
+from tests.dp_util import dp_data as _data, dp_init as _init, gloo_rank, two_ranks
+from tests.engine_util import factor_batch, tiny_nets as _factor_nets, tiny_spec as _spec
+from tests.simutil import sim_lib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _spec():
-  enc = [('center',), ('conv', 8, 4, 2, 'elu'), ('conv', 16, 4, 2, 'elu'), ('flatten',),
-         ('dense', 24, 'linear')]
-  dec = [('dense', 32, 'linear'), ('reshape', (2, 2, 8)), ('deconv', 16, 4, 2, 'elu'),
-         ('deconv', 8, 4, 2, 'elu'), ('conv', 1, 1, 1, 'linear')]
-  return enc, dec, (8, 8, 1), 4
-
-
-def _data(B):
-  rng = np.random.default_rng(5)
-  x = np.clip(rng.random((B, 8, 8, 1)), 1e-6, 1 - 1e-6).astype(np.float32)
-  eps = rng.standard_normal((B, 4)).astype(np.float32)
-  return torch.tensor(x), torch.tensor(eps)
-
-
-def _init(eng):
-  g = torch.Generator().manual_seed(0)
-  eng.params.copy_(torch.randn(eng.params.numel(), generator=g) * 0.1)
-
-
 def _worker(rank, world, port, out_path, tc=None, buckets=None, segmented=False):
   sys.path.insert(0, ROOT)
-  from odin_ai_amd import _lib
   from odin_ai_amd.dist import shard_batch
   from odin_ai_amd.engine import VAEEngine
-  os.environ['MASTER_ADDR'] = '127.0.0.1'
-  os.environ['MASTER_PORT'] = str(port)
-  dist.init_process_group('gloo', rank=rank, world_size=world)
-  L = _lib.Lib(os.path.join(ROOT, 'tests', 'sim', 'libodin_sim.so'))
+  L = gloo_rank(rank, world, port)
   enc, dec, shp, D = _spec()
   B = 8
   x, eps = _data(B)
@@ -67,23 +45,21 @@ def _worker(rank, world, port, out_path, tc=None, buckets=None, segmented=False)
   dist.destroy_process_group()
 
 
-def test_two_gloo_ranks_match_single_rank(tmp_path):
+def _single_rank(L, tc=None):
+  """the three steps of _worker on one rank and the whole batch"""
   from odin_ai_amd.engine import VAEEngine
-  from tests.simutil import sim_lib
-  L = sim_lib()
-  s = socket.socket()
-  s.bind(('127.0.0.1', 0))
-  port = s.getsockname()[1]
-  s.close()
-  out = str(tmp_path / 'p2.pt')
-  mp.spawn(_worker, args=(2, port, out), nprocs=2, join=True)
-  p2 = torch.load(out)['params']
-  enc, dec, shp, D = _spec()
   x, eps = _data(8)
-  eng = VAEEngine(enc, dec, shp, D, 8, 'cpu', lib=L, world_size=1)
+  eng = VAEEngine(*_spec(), 8, 'cpu', lib=L, world_size=1, tc=tc)
   _init(eng)
   for _ in range(3):
     eng.train_step(x, eps, lr=1e-3, beta=4.0, global_clipnorm=100.0)
+  return eng
+
+
+def test_two_gloo_ranks_match_single_rank(tmp_path):
+  L = sim_lib()
+  p2 = two_ranks(tmp_path, _worker)['params']
+  eng = _single_rank(L)
   d = (eng.params - p2).abs()
   # identical maths, different fp32 summation order (per-rank partial sums): Adam's
   # normalisation bounds the per-step drift by a fraction of lr
@@ -95,22 +71,9 @@ def test_beta_tc_two_ranks_match_single_rank(tmp_path):
   parallelism it is evaluated on the GLOBAL batch (all-gather of (p, z), this rank's rows against
   all posteriors, reduce-scatter of the posterior-side gradients): 2 ranks x 4 samples must
   reproduce 1 rank x 8 samples -- TC value, loss and parameters after 3 Adam steps."""
-  from odin_ai_amd.engine import VAEEngine
-  from tests.simutil import sim_lib
   L = sim_lib()
-  s = socket.socket()
-  s.bind(('127.0.0.1', 0))
-  port = s.getsockname()[1]
-  s.close()
-  out = str(tmp_path / 'tc2.pt')
-  mp.spawn(_worker, args=(2, port, out, 'betatc'), nprocs=2, join=True)
-  r2 = torch.load(out)
-  enc, dec, shp, D = _spec()
-  x, eps = _data(8)
-  eng = VAEEngine(enc, dec, shp, D, 8, 'cpu', lib=L, world_size=1, tc='betatc')
-  _init(eng)
-  for _ in range(3):
-    eng.train_step(x, eps, lr=1e-3, beta=4.0, global_clipnorm=100.0)
+  r2 = two_ranks(tmp_path, _worker, 'betatc')
+  eng = _single_rank(L, 'betatc')
   # out4 = [loss, mean llk, mean beta*kl, tc]: llk / kl are per-rank means (ranks differ), the TC
   # term is global and must agree
   assert abs(eng.out4[3].item() - r2['out4'][3].item()) < 1e-4 * max(1.0, abs(eng.out4[3].item()))
@@ -123,42 +86,12 @@ def test_segmented_program_two_ranks_match_single_rank(tmp_path, tc, buckets, ki
   """the data-parallel step as kernel segments around its collectives
   (A | all-gather | B | reduce-scatter | C | all-reduce | D; two gradient buckets: decoder bucket reduced
   before the encoder's backward pass ends) gives the single-rank result."""
-  from odin_ai_amd.engine import VAEEngine
-  from tests.simutil import sim_lib
   L = sim_lib()
-  s = socket.socket()
-  s.bind(('127.0.0.1', 0))
-  port = s.getsockname()[1]
-  s.close()
-  out = str(tmp_path / 'seg.pt')
-  mp.spawn(_worker, args=(2, port, out, tc, buckets, True), nprocs=2, join=True)
-  r2 = torch.load(out)
+  r2 = two_ranks(tmp_path, _worker, tc, buckets, True)
   assert r2['kinds'] == kinds, r2['kinds']
-  enc, dec, shp, D = _spec()
-  x, eps = _data(8)
-  eng = VAEEngine(enc, dec, shp, D, 8, 'cpu', lib=L, world_size=1, tc=tc)
-  _init(eng)
-  for _ in range(3):
-    eng.train_step(x, eps, lr=1e-3, beta=4.0, global_clipnorm=100.0)
+  eng = _single_rank(L, tc)
   d = (eng.params - r2['params']).abs()
   assert d.max().item() < 2e-4 and d.mean().item() < 2e-6, (d.max().item(), d.mean().item())
-
-
-def _factor_nets():
-  from odin_ai_amd.networks import RVconf, SequentialNetwork
-  enc, dec, shp, D = _spec()
-  return dict(encoder=SequentialNetwork(enc, 'Encoder', shp), decoder=SequentialNetwork(dec, 'Decoder', (D,)),
-              observation=RVconf(shp, 'bernoulli', projection=False, name='image'),
-              latents=RVconf((D,), 'mvndiag', projection=True, name='latents'))
-
-
-def _factor_data():
-  rng = np.random.default_rng(6)
-  B1, D = 4, 4
-  x = np.clip(rng.random((2 * B1, 8, 8, 1)), 1e-6, 1 - 1e-6).astype(np.float32)
-  eps, eps2 = (rng.standard_normal((B1, D)).astype(np.float32) for _ in range(2))
-  perm = np.stack([rng.permutation(B1) for _ in range(D)], 1).astype(np.int32)
-  return B1, x, eps, eps2, perm
 
 
 def _factor_run(fv, x, eps, eps2, perm):
@@ -170,13 +103,9 @@ def _factor_run(fv, x, eps, eps2, perm):
 
 def _factor_worker(rank, world, port, out_path):
   sys.path.insert(0, ROOT)
-  from odin_ai_amd import _lib
   from odin_ai_amd.vae import FactorVAE
-  os.environ['MASTER_ADDR'] = '127.0.0.1'
-  os.environ['MASTER_PORT'] = str(port)
-  dist.init_process_group('gloo', rank=rank, world_size=world)
-  L = _lib.Lib(os.path.join(ROOT, 'tests', 'sim', 'libodin_sim.so'))
-  B1, x, eps, eps2, perm = _factor_data()
+  L = gloo_rank(rank, world, port)
+  B1, (x, eps, eps2, perm) = 4, factor_batch(6)
   h = B1 // world
   sl = slice(rank * h, (rank + 1) * h)
   # this rank's shard: its rows of x1 followed by its rows of x2; the permutation stays GLOBAL
@@ -192,16 +121,9 @@ def test_factor_vae_two_ranks_match_single_rank(tmp_path):
   """FactorVAE under data parallelism: global permute_dims (all-gather of z'), both gradient
   buckets all-reduced, replicas start from rank 0's weights -- 2 ranks x (2+2) == 1 rank x (4+4)."""
   from odin_ai_amd.vae import FactorVAE
-  from tests.simutil import sim_lib
   L = sim_lib()
-  s = socket.socket()
-  s.bind(('127.0.0.1', 0))
-  port = s.getsockname()[1]
-  s.close()
-  out = str(tmp_path / 'f2.pt')
-  mp.spawn(_factor_worker, args=(2, port, out), nprocs=2, join=True)
-  r2 = torch.load(out)
-  B1, x, eps, eps2, perm = _factor_data()
+  r2 = two_ranks(tmp_path, _factor_worker)
+  B1, (x, eps, eps2, perm) = 4, factor_batch(6)
   fv = FactorVAE(discriminator_units=(16, 16), device='cpu', lib=L, **_factor_nets())
   p, dpar, _ = _factor_run(fv, x, eps, eps2, perm)
   d1, d2 = (p - r2['p']).abs(), (dpar - r2['d']).abs()

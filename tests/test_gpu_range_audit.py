@@ -8,7 +8,7 @@ import torch
 
 from oracle import vae_oracle as vo
 from tests.parity_util import relerr
-from tests.range_audit import RangeAudit
+from tests.range_audit import RangeAudit, bern_targets
 
 pytestmark = pytest.mark.gpu
 
@@ -114,14 +114,6 @@ def _vs_f64(dev, L, spec, B, x, eps, P, obs='bernoulli', fused=True, audit=True,
   return eng
 
 
-def _bern_targets(shape, seed=3):
-  rng = np.random.default_rng(seed)
-  x = rng.uniform(-2.0, 6.0, size=shape)
-  x.reshape(-1)[::5] = 0.0
-  x.reshape(-1)[1::5] = 1.0
-  return x.astype(np.float32)
-
-
 @pytest.mark.parametrize('spec,B,fused', [('mnist_dense', 128, True), ('dsprites', 32, False), ('dsprites', 32, True)])
 def test_bernoulli_targets_outside_unit_interval(dev, L, spec, B, fused):
   """targets in [-2, 6] and exact 0 / 1: the stand-alone ELBO kernel (dense MNIST; the unfused dSprites step) and the
@@ -132,7 +124,7 @@ def test_bernoulli_targets_outside_unit_interval(dev, L, spec, B, fused):
   eps = rng.standard_normal((B, zdim)).astype(np.float32)
   P = vo.OracleVAE(enc, dec, in_shape, zdim).init_params(seed=9)
   P = {k: v.astype(np.float32).astype(np.float64) for k, v in P.items()}
-  _vs_f64(dev, L, s, B, _bern_targets((B,) + tuple(in_shape)), eps, P, fused=fused)
+  _vs_f64(dev, L, s, B, bern_targets((B,) + tuple(in_shape)).astype(np.float32), eps, P, fused=fused)
 
 
 def test_bernoulli_unit_targets_need_no_absmax(dev, L):

@@ -3,32 +3,20 @@
 and the DIP moments / finish pair (moment blocks all-gathered), through the segmented step program, 1 and 2 gradient
 buckets."""
 import os
-import socket
 import sys
 
 import numpy as np
 import pytest
 import torch
 import torch.distributed as dist
-import torch.multiprocessing as mp
+
+from tests.dp_util import dp_data as _data, dp_init as _init, gloo_rank, two_ranks
+from tests.engine_util import tiny_spec as _spec
+from tests.simutil import sim_lib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REG = dict(mmd=dict(latent_reg='mmd', reg_coef=5.0, mmd_prior_samples=11),
            dip_ii=dict(latent_reg='dip_ii', reg_coef=1.0, dip_lambda=(1.5, 2.5)))
-
-
-def _spec():
-  enc = [('center',), ('conv', 8, 4, 2, 'elu'), ('conv', 16, 4, 2, 'elu'), ('flatten',), ('dense', 24, 'linear')]
-  dec = [('dense', 32, 'linear'), ('reshape', (2, 2, 8)), ('deconv', 16, 4, 2, 'elu'), ('deconv', 8, 4, 2, 'elu'),
-         ('conv', 1, 1, 1, 'linear')]
-  return enc, dec, (8, 8, 1), 4
-
-
-def _data(B):
-  rng = np.random.default_rng(5)
-  x = np.clip(rng.random((B, 8, 8, 1)), 1e-6, 1 - 1e-6).astype(np.float32)
-  eps = rng.standard_normal((B, 4)).astype(np.float32)
-  return torch.tensor(x), torch.tensor(eps)
 
 
 def _run(eng, xs, es, world):
@@ -45,21 +33,16 @@ def _run(eng, xs, es, world):
 
 def _worker(rank, world, port, out_path, reg, buckets):
   sys.path.insert(0, ROOT)
-  from odin_ai_amd import _lib
   from odin_ai_amd.dist import shard_batch
   from odin_ai_amd.engine import VAEEngine
-  os.environ['MASTER_ADDR'] = '127.0.0.1'
-  os.environ['MASTER_PORT'] = str(port)
-  dist.init_process_group('gloo', rank=rank, world_size=world)
-  L = _lib.Lib(os.path.join(ROOT, 'tests', 'sim', 'libodin_sim.so'))
+  L = gloo_rank(rank, world, port)
   enc, dec, shp, D = _spec()
   B = 8
   x, eps = _data(B)
   # (each rank its own engine seed, as bench.py and the model API give them; the prior seed is shared)
   eng = VAEEngine(enc, dec, shp, D, B // world, 'cpu', lib=L, world_size=world, seed=1 + rank, dp_buckets=buckets,
                   prior_seed=3, **REG[reg])
-  g = torch.Generator().manual_seed(0)
-  eng.params.copy_(torch.randn(eng.params.numel(), generator=g) * 0.1)
+  _init(eng)
   out4, kinds = _run(eng, shard_batch(x, rank, world), shard_batch(eps, rank, world), world)
   if rank == 0:
     torch.save(dict(params=eng.params.clone(), out4=out4, kinds=kinds), out_path)
@@ -70,20 +53,12 @@ def _worker(rank, world, port, out_path, reg, buckets):
 @pytest.mark.parametrize('reg', sorted(REG))
 def test_two_gloo_ranks_match_single_rank(tmp_path, reg, buckets):
   from odin_ai_amd.engine import VAEEngine
-  from tests.simutil import sim_lib
   L = sim_lib()
-  s = socket.socket()
-  s.bind(('127.0.0.1', 0))
-  port = s.getsockname()[1]
-  s.close()
-  out = str(tmp_path / 'p2.pt')
-  mp.spawn(_worker, args=(2, port, out, reg, buckets), nprocs=2, join=True)
-  r2 = torch.load(out)
+  r2 = two_ranks(tmp_path, _worker, reg, buckets)
   enc, dec, shp, D = _spec()
   x, eps = _data(8)
   eng = VAEEngine(enc, dec, shp, D, 8, 'cpu', lib=L, prior_seed=3, **REG[reg])
-  g = torch.Generator().manual_seed(0)
-  eng.params.copy_(torch.randn(eng.params.numel(), generator=g) * 0.1)
+  _init(eng)
   out1, kinds1 = _run(eng, x, eps, 1)
   assert 'c' not in kinds1
   # MMD: (k | all-gather | shard | all-reduce | finalise ...); DIP: (k | all-gather | finish ...)

@@ -13,6 +13,8 @@ from odin_ai_amd.losses import disentangled_inferred_prior_loss, maximum_mean_di
 from odin_ai_amd.vae import DIPVAE, BetaVAE, InfoVAE, MVNDiagPosterior, get_vae
 from oracle import vae_oracle as vo
 from oracle.torch_ref import TorchVAE
+from tests.engine_util import neck_spec, tiny_batch, tiny_nets as api_nets, tiny_spec
+from tests.parity_util import oracle_params
 
 
 @pytest.fixture(scope='module')
@@ -250,21 +252,6 @@ def t_dip(loc, scale, only_mean, lo=2.0, ld=1.0):
   return lo * (off ** 2).sum() + ld * ((dg - 1.0) ** 2).sum()
 
 
-def tiny_spec(zdim=4):
-  enc = [('center',), ('conv', 8, 4, 2, 'elu'), ('conv', 16, 4, 2, 'elu'), ('flatten',), ('dense', 24, 'linear')]
-  dec = [('dense', 32, 'linear'), ('reshape', (2, 2, 8)), ('deconv', 16, 4, 2, 'elu'), ('deconv', 8, 4, 2, 'elu'),
-         ('conv', 1, 1, 1, 'linear')]
-  return enc, dec, (8, 8, 1), zdim
-
-
-def neck_spec(zdim=5, proj=128):
-  """the neck of the dSprites stack under a shortened encoder / decoder (tests/test_sim_engine.py's neck_spec)"""
-  enc = [('center',), ('conv', 64, 4, 2, 'elu'), ('conv', 64, 4, 2, 'elu'), ('flatten',), ('dense', proj, 'linear')]
-  dec = [('dense', proj, 'linear'), ('reshape', (4, 4, proj // 16)), ('deconv', 64, 4, 2, 'elu'),
-         ('deconv', 8, 4, 2, 'elu'), ('conv', 1, 1, 1, 'linear')]
-  return enc, dec, (16, 16, 1), zdim
-
-
 REG = dict(mmd=dict(latent_reg='mmd', reg_coef=3.5, mmd_prior_samples=9),
            mmd_linear=dict(latent_reg='mmd', reg_coef=0.5, mmd_prior_samples=5, mmd_kernel='linear'),
            dip_i=dict(latent_reg='dip_i', reg_coef=1.0, dip_lambda=(1.5, 2.5)),
@@ -344,25 +331,6 @@ def test_latent_reg_argument_errors(bk):
 
 
 # ---- 3. model API ---------------------------------------------------------------------------------------------------
-def api_nets(zdim=4):
-  from odin_ai_amd.networks import RVconf, SequentialNetwork
-  enc, dec, in_shape, _ = tiny_spec(zdim)
-  return dict(encoder=SequentialNetwork(enc, 'Encoder', in_shape), decoder=SequentialNetwork(dec, 'Decoder', (zdim,)),
-              observation=RVconf(in_shape, 'bernoulli', projection=False, name='image'),
-              latents=RVconf((zdim,), 'mvndiag', projection=True, name='latents'))
-
-
-def oracle_params(vae):
-  return {k: v.detach().cpu().numpy(force=True).astype(np.float64) for k, v in vae.trainable_variables.items()}
-
-
-def _model_case(B=6, zdim=4, seed=2):
-  rng = np.random.default_rng(seed)
-  x = np.clip(rng.random((B, 8, 8, 1)), 1e-6, 1 - 1e-6).astype(np.float32)
-  eps = rng.standard_normal((B, zdim)).astype(np.float32)
-  return x, eps
-
-
 def _adam_ref(P, G, M, V, t, lr):
   b1, b2, e = 0.9, 0.999, 1e-7
   a = lr * np.sqrt(1 - b2 ** t) / (1 - b1 ** t)
@@ -385,7 +353,7 @@ def test_model_api(L, DEV, which):
     vae = DIPVAE(only_mean=which == 'dip_i', lambda_diag=1.5, lambda_offdiag=2.5, beta=2.0, device=DEV, lib=L, **nets)
     coef, key, kw = 1.0, 'dip_latents', dict(latent_reg=which, reg_coef=1.0, dip_lambda=(1.5, 2.5))
   beta = vae.beta
-  x, eps = _model_case()
+  x, eps = tiny_batch(2)
   eng = vae._engine(6)
   P = oracle_params(vae)
   tv = TorchVAE(nets['encoder'].layers, nets['decoder'].layers, (8, 8, 1), 4, beta=beta)
@@ -428,7 +396,7 @@ def test_model_api(L, DEV, which):
 
 def test_model_api_sample_shape_and_fit(L, DEV):
   vae = DIPVAE(beta=1.5, sample_shape=2, analytic=True, device=DEV, lib=L, **api_nets())
-  x, eps = _model_case()
+  x, eps = tiny_batch(2)
   eps2 = np.random.default_rng(3).standard_normal((12, 4)).astype(np.float32)
   llk, kl = vae.elbo_components(x, eps=eps2)
   assert llk['llk_image'].shape == (2, 6) and kl['dip_latents'].dim() == 0

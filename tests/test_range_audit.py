@@ -10,9 +10,9 @@ import torch
 from odin_ai_amd.engine import VAEEngine
 from oracle import vae_oracle as vo
 from tests.parity_util import check_engine_vs_oracle, make_case
-from tests.range_audit import RangeAudit
+from tests.range_audit import RangeAudit, bern_targets
 from tests.simutil import sim_lib
-from tests.test_sim_engine import neck_spec, tiny16_spec, tiny_conv_spec
+from tests.engine_util import dense_spec, head_spec, neck_spec, tiny16_spec, tiny_spec
 
 
 @pytest.fixture(scope='module')
@@ -45,19 +45,16 @@ def audited_steps(eng, x, eps, betas=BETAS, fused=True, clip=100.0):
 
 def _spec(name, C=1):
   if name == 'gauss':
-    e, d, s, z = tiny_conv_spec(C)
-    return e, d[:-1] + [('conv', 2 * C, 1, 1, 'linear')], s, z
+    return head_spec(2 * C, 5, C)
   if name == 'mixql':
-    e, d, s, z = tiny_conv_spec(C)
-    return e, d[:-1] + [('conv', 10 * vo.mixql_n_out(C), 1, 1, 'linear')], s, z
+    return head_spec(10 * vo.mixql_n_out(C), 5, C)
   if name == 'tiny16':
     return tiny16_spec(C)
   if name == 'neck':
-    return neck_spec(C, 5, 128)
+    return neck_spec(5, 128, C)
   if name == 'mnist_dense':
-    return ([('flatten',), ('dense', 40, 'relu'), ('dense', 24, 'relu')],
-            [('dense', 24, 'relu'), ('dense', 784, 'linear'), ('reshape', (28, 28, 1))], (28, 28, 1), 4)
-  return tiny_conv_spec(C)
+    return dense_spec(28)
+  return tiny_spec(5, C)
 
 
 AUDIT_CASES = [
@@ -100,7 +97,7 @@ def test_range_words_model_api_sequence(L):
   """encode -> decode -> optimize: the step after two forward-only passes starts from words the forward passes wrote
   (VAEEngine._clear_stale_act_words): the audit of the optimize step sees no stale activation word"""
   B = 3
-  enc, dec, in_shape, zdim, x, eps = make_case(tiny_conv_spec(1), 'bernoulli', B)
+  enc, dec, in_shape, zdim, x, eps = make_case(tiny_spec(5), 'bernoulli', B)
   eng = VAEEngine(enc, dec, in_shape, zdim, B, 'cpu', lib=L)
   g = torch.Generator().manual_seed(2)
   eng.params.copy_(torch.randn(eng.params.numel(), generator=g) * 0.1)
@@ -117,21 +114,13 @@ def test_range_words_model_api_sequence(L):
 
 
 # ---- Bernoulli targets outside [0, 1] ------------------------------------------------------------------------------
-def _bern_targets(shape, seed=3):
-  rng = np.random.default_rng(seed)
-  x = rng.uniform(-2.0, 6.0, size=shape)
-  x.reshape(-1)[::5] = 0.0
-  x.reshape(-1)[1::5] = 1.0
-  return x
-
-
 @pytest.mark.parametrize('spec,fused', [('mnist_dense', True), ('tiny', False), ('tiny16', True)])
 def test_bernoulli_targets_outside_unit_interval(L, spec, fused):
   """the reference's Bernoulli log-prob takes any real target: targets in [-2, 6] (and exact 0 / 1) on the stand-alone
   ELBO kernel (MNIST dense, the unfused conv step) and the fused tail -- no NaN flag, loss and gradients as float64"""
   B = 3
   enc, dec, in_shape, zdim, _, eps = make_case(_spec(spec), 'bernoulli', B)
-  x = _bern_targets((B,) + tuple(in_shape))
+  x = bern_targets((B,) + tuple(in_shape))
   model = vo.OracleVAE(enc, dec, in_shape, zdim, observation='bernoulli', beta=1.0)
   P = model.init_params(seed=11)
   eng = VAEEngine(enc, dec, in_shape, zdim, B, 'cpu', observation='bernoulli', lib=L)

@@ -5,6 +5,7 @@ import torch
 
 from odin_ai_amd.engine import VAEEngine
 from oracle import vae_oracle as vo
+from tests.engine_util import dense_spec, head_spec, neck_spec, tiny16_spec, tiny_spec
 from tests.parity_util import check_engine_vs_oracle, make_case
 from tests.simutil import sim_lib
 
@@ -12,22 +13,6 @@ from tests.simutil import sim_lib
 @pytest.fixture(scope='module')
 def L():
   return sim_lib()
-
-
-def tiny_conv_spec(C=1, zdim=5):
-  enc = [('center',), ('conv', 8, 4, 2, 'elu'), ('conv', 16, 4, 2, 'elu'), ('flatten',),
-         ('dense', 24, 'linear')]
-  dec = [('dense', 32, 'linear'), ('reshape', (2, 2, 8)), ('deconv', 16, 4, 2, 'elu'),
-         ('deconv', 8, 4, 2, 'elu'), ('conv', C, 1, 1, 'linear')]
-  return enc, dec, (8, 8, C), zdim
-
-
-def tiny16_spec(C=1, zdim=5):
-  enc = [('center',), ('conv', 8, 4, 2, 'elu'), ('conv', 16, 4, 2, 'elu'), ('flatten',),
-         ('dense', 24, 'linear')]
-  dec = [('dense', 128, 'linear'), ('reshape', (4, 4, 8)), ('deconv', 16, 4, 2, 'elu'),
-         ('deconv', 8, 4, 2, 'elu'), ('conv', C, 1, 1, 'linear')]
-  return enc, dec, (16, 16, C), zdim
 
 
 CASES = [
@@ -50,22 +35,15 @@ CASES = [
 def test_engine_step_matches_oracle(L, name, kw, obs, C):
   B = 6
   if name == 'mnist_dense':
-    spec = vo.mnist_dense_spec(4)
-    spec = ([('flatten',), ('dense', 40, 'relu'), ('dense', 24, 'relu')],
-            [('dense', 24, 'relu'), ('dense', 784, 'linear'), ('reshape', (28, 28, 1))],
-            (28, 28, 1), 4)
+    spec = dense_spec(28)
   elif name == 'tiny_gauss':
-    e, d, s, z = tiny_conv_spec(C)
-    d = d[:-1] + [('conv', 2 * C, 1, 1, 'linear')]
-    spec = (e, d, s, z)
+    spec = head_spec(2 * C, 5, C)
   elif name == 'tiny_mixql':
-    e, d, s, z = tiny_conv_spec(C)
-    d = d[:-1] + [('conv', 10 * vo.mixql_n_out(C), 1, 1, 'linear')]
-    spec = (e, d, s, z)
+    spec = head_spec(10 * vo.mixql_n_out(C), 5, C)
   elif name.startswith('tiny16'):
     spec = tiny16_spec(C)
   else:
-    spec = tiny_conv_spec(C)
+    spec = tiny_spec(5, C)
   enc, dec, in_shape, zdim, x, eps = make_case(spec, obs, B)
   model = vo.OracleVAE(enc, dec, in_shape, zdim, observation=obs, **kw)
   P = model.init_params(seed=11)
@@ -92,14 +70,10 @@ CUSTOM = [
      [('center',), ('conv', 8, 4, 2, 'elu'), ('conv', 16, 4, 2, 'elu'), ('flatten',), ('dense', 24, 'linear')],
      [('dense', 8 * 8 * 8, 'linear'), ('reshape', (8, 8, 8)), ('deconv', 8, 4, 2, 'elu'),
       ('conv', 8, 4, 1, 'elu'), ('conv', 1, 1, 1, 'linear')], (16, 16, 1), 5),
-    ('five_by_five',
-     [('center',), ('conv', 8, 5, 1, 'elu'), ('conv', 8, 5, 2, 'elu'), ('flatten',), ('dense', 20, 'linear')],
-     [('dense', 7 * 7 * 4, 'linear'), ('reshape', (7, 7, 4)), ('deconv', 8, 5, 2, 'elu'), ('conv', 8, 5, 1, 'elu'),
-      ('conv', 1, 1, 1, 'linear')], (14, 14, 1), 3),
-    ('five_by_five',
-     [('center',), ('conv', 8, 5, 1, 'elu'), ('conv', 8, 5, 2, 'elu'), ('flatten',), ('dense', 20, 'linear')],
-     [('dense', 7 * 7 * 4, 'linear'), ('reshape', (7, 7, 4)), ('deconv', 8, 5, 2, 'elu'), ('conv', 8, 5, 1, 'elu'),
-      ('conv', 1, 1, 1, 'linear')], (14, 14, 1), 11),
+    *[('five_by_five',
+       [('center',), ('conv', 8, 5, 1, 'elu'), ('conv', 8, 5, 2, 'elu'), ('flatten',), ('dense', 20, 'linear')],
+       [('dense', 7 * 7 * 4, 'linear'), ('reshape', (7, 7, 4)), ('deconv', 8, 5, 2, 'elu'), ('conv', 8, 5, 1, 'elu'),
+        ('conv', 1, 1, 1, 'linear')], (14, 14, 1), B) for B in (3, 11)],
 ]
 
 
@@ -121,20 +95,11 @@ def test_first_deconv_with_any_latent_width(L, zdim):
   check_engine_vs_oracle(eng, model, P, x, eps, beta=2.0, steps=2, clip=100.0)
 
 
-def neck_spec(C=1, zdim=5, proj=128):
-  """the neck of the dSprites / Shapes3D stacks (image_networks.py:466-471, 494-502) under a shortened encoder / decoder:
-  ... -> [8, 8, 64] -> Conv2D(64, 4, 2) -> Flatten -> Dense(proj) | Dense(proj) -> (4, 4, proj / 16) -> deconv 64 -> ..."""
-  enc = [('center',), ('conv', 64, 4, 2, 'elu'), ('conv', 64, 4, 2, 'elu'), ('flatten',), ('dense', proj, 'linear')]
-  dec = [('dense', proj, 'linear'), ('reshape', (4, 4, proj // 16)), ('deconv', 64, 4, 2, 'elu'),
-         ('deconv', 8, 4, 2, 'elu'), ('conv', C, 1, 1, 'linear')]
-  return enc, dec, (16, 16, C), zdim
-
-
 @pytest.mark.parametrize('B,zdim,proj,kw', [(3, 5, 128, dict(beta=2.0)), (2, 6, 256, dict(beta=1.0, analytic=True, free_bits=0.3))])
 def test_neck_step_matches_oracle(L, B, zdim, proj, kw):
   """conv3 .. deconv1 as one launch per direction (neck.hip) inside a whole training step, odd batch (a workgroup with
   one sample) and odd latent width (misaligned decoder weights) included"""
-  enc, dec, in_shape, zd, x, eps = make_case(neck_spec(1, zdim, proj), 'bernoulli', B)
+  enc, dec, in_shape, zd, x, eps = make_case(neck_spec(zdim, proj), 'bernoulli', B)
   model = vo.OracleVAE(enc, dec, in_shape, zd, observation='bernoulli', **kw)
   P = model.init_params(seed=6)
   eng = VAEEngine(enc, dec, in_shape, zd, B, 'cpu', observation='bernoulli', lib=L,
@@ -171,7 +136,7 @@ def test_custom_decoders_keep_valid_range_words(L, name, enc, dec, in_shape, B):
 
 def _run_steps(L, ring, lrs, betas, schedule=None, n=None, clip=100.0, rows=128, fuse_norm=True, jump=None):
   """`jump` = (after step i, set step_count to v): what vae.py does when another engine ran steps in between"""
-  enc, dec, in_shape, zdim = tiny_conv_spec(1)
+  enc, dec, in_shape, zdim = tiny_spec(5)
   B = 2   # (what is compared here is the scalar plumbing: the smallest batch keeps the simulated steps short)
   eng = VAEEngine(enc, dec, in_shape, zdim, B, 'cpu', lib=L, hyper_ring=ring, hyper_ring_rows=rows,
                   fuse_norm=fuse_norm)

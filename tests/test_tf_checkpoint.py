@@ -119,9 +119,8 @@ def test_model_loads_keras_shaped_checkpoint(bk):
   import tempfile
   with tempfile.TemporaryDirectory() as d:
     expected = gen.build(d)
-  enc = [('center',), ('conv', 8, 4, 2, 'elu'), ('conv', 16, 4, 2, 'elu'), ('flatten',), ('dense', 24, 'linear')]
-  dec = [('dense', 32, 'linear'), ('reshape', (2, 2, 8)), ('deconv', 16, 4, 2, 'elu'), ('deconv', 8, 4, 2, 'elu'),
-         ('conv', 1, 1, 1, 'linear')]
+  from tests.engine_util import tiny_spec
+  enc, dec, _, _ = tiny_spec()
   nets = dict(encoder=SequentialNetwork(enc, 'Encoder', (8, 8, 1), ['encoder0', 'encoder1', 'encoder_proj']),
               decoder=SequentialNetwork(dec, 'Decoder', (4,), ['decoder_proj', 'decoder1', 'decoder2', 'decoder6']),
               observation=RVconf((8, 8, 1), 'bernoulli', projection=False, name='image'),

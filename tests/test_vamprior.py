@@ -9,9 +9,10 @@ import torch
 from odin_ai_amd.engine import VAEEngine
 from oracle import vae_oracle as vo
 from oracle.torch_ref import TorchVAE, t_seq
+from tests.engine_util import launch_record, neck_spec, tiny_batch, tiny_spec
 from tests.range_audit import RangeAudit
-from tests.test_latent_regularizers import (_adam_ref, _Hip, _st, api_nets, assert_grad, assert_value, neck_spec,
-                                            np_softplus, oracle_params, tiny_spec)
+from tests.test_latent_regularizers import (_adam_ref, _Hip, _st, api_nets, assert_grad, assert_value, np_softplus,
+                                            oracle_params)
 
 LO, HI = 1e-6, 1.0 - 1e-6
 LOG2PI = float(np.log(2.0 * np.pi))
@@ -332,44 +333,12 @@ PLAIN_STEP_CALLS = [
     'odin_wgrad_planes_defer_end', 'odin_slab_reduce_sumsq', 'odin_slab_reduce_sumsq', 'odin_adam_ring_parts']
 
 
-def _launch_record(bk, steps=1, **kw):
-  """train_steps of a tiny engine; -> (engine, the names of every library call of the LAST step, in order)"""
-  enc, dec, in_shape, zdim = tiny_spec()
-  calls = []
-  eng = VAEEngine(enc, dec, in_shape, zdim, 4, bk.dev, lib=bk.L, **kw)
-
-  class Rec:
-    def __init__(self, L):
-      self._L = L
-
-    def __getattr__(self, name):
-      fn = getattr(self._L, name)
-      if not name.startswith('odin_'):
-        return fn
-
-      def call(*a):
-        calls.append(name)
-        return fn(*a)
-      return call
-  eng.lib = Rec(bk.L)
-  eng.enc.lib = eng.dec.lib = eng.lib
-  if getattr(eng, 'vamp_K', None) is not None:
-    eng.penc.lib = eng.lib
-  rng = np.random.default_rng(3)
-  x = bk.T(np.clip(rng.random((4,) + in_shape), 1e-6, 1 - 1e-6))
-  eps = bk.T(rng.standard_normal((4, zdim)))
-  for _ in range(steps):
-    calls.clear()
-    eng.train_step(x, eps, lr=1e-3, beta=2.0)
-  return eng, calls
-
-
 def test_plain_step_issues_the_launches_it_issued_before(bk):
   """an engine built without any of the new keywords: the recorded call list of the commit before, first step and
   steady state (this test passes on that commit too)"""
-  eng, c1 = _launch_record(bk)
+  eng, c1 = launch_record(bk)
   assert c1 == PLAIN_STEP_CALLS
-  _, c2 = _launch_record(bk, steps=2)
+  _, c2 = launch_record(bk, steps=2)
   steady = list(PLAIN_STEP_CALLS)
   steady.remove('odin_slab_reduce_sumsq')   # (the dry run happens once)
   assert c2 == steady
@@ -379,12 +348,12 @@ def test_plain_step_issues_the_launches_it_issued_before(bk):
 
 
 def test_vamprior_keyword_none_is_the_plain_engine_and_k_adds_the_pseudo_pass(bk):
-  eng0, c0 = _launch_record(bk)
-  eng1, c1 = _launch_record(bk, vamprior_components=None, pseudoinputs_mean=0.3, pseudoinputs_std=2.0)
+  eng0, c0 = launch_record(bk)
+  eng1, c1 = launch_record(bk, vamprior_components=None, pseudoinputs_mean=0.3, pseudoinputs_std=2.0)
   assert c1 == PLAIN_STEP_CALLS and eng1.vamp_K is None and not hasattr(eng1, 'penc')
   assert eng0.params.numel() == eng1.params.numel() and eng0.range_words.numel() == eng1.range_words.numel()
   # with K: the pseudo pass's launches appear, the parameter buffer grows by K * prod(in_shape)
-  eng2, c2 = _launch_record(bk, vamprior_components=3)
+  eng2, c2 = launch_record(bk, vamprior_components=3)
   assert c2.count('odin_vamprior_fwd_bwd') == 1 and c2.count('odin_clip_range_fwd') == 1
   assert c2.count('odin_clip_range_bwd') == 1 and c2.count('odin_slab_reduce') + c2.count('odin_slab_reduce_sumsq') >= 1
   assert eng2.layout.entries[-1][0] == ('vamp', 'u') and eng2.n_params == eng0.n_params + 3 * 64
@@ -447,12 +416,6 @@ def _vamp_model(L, DEV, K=5, beta=2.0, **kw):
   return vae, u, idx
 
 
-def _api_case(B=6, zdim=4, seed=2):
-  rng = np.random.default_rng(seed)
-  return (np.clip(rng.random((B, 8, 8, 1)), 1e-6, 1 - 1e-6).astype(np.float32),
-          rng.standard_normal((B, zdim)).astype(np.float32))
-
-
 def test_api_names_and_defaults(bk):
   from odin_ai_amd.interpolation import Interpolation
   from odin_ai_amd.vae import BetaVAE, Vamprior, VampriorVAE, get_vae
@@ -476,7 +439,7 @@ def test_api_names_and_defaults(bk):
 def test_api_elbo_and_optimize(bk):
   L, DEV = bk.L, bk.dev
   vae, u, idx = _vamp_model(L, DEV)
-  x, eps = _api_case()
+  x, eps = tiny_batch(2)
   spec = (api_nets()['encoder'].layers, api_nets()['decoder'].layers, (8, 8, 1), 4)
   P = oracle_params(vae)
   assert np.array_equal(P[('vamp', 'u')], u.astype(np.float64))
@@ -559,7 +522,7 @@ def test_api_sampling(bk):
 def test_api_marginal_log_prob_uses_the_mixture(bk):
   L, DEV = bk.L, bk.dev
   vae, u, idx = _vamp_model(L, DEV, K=5)
-  x, _ = _api_case(B=3)
+  x, _ = tiny_batch(2, 3)
   n = 4
   eps = np.random.default_rng(8).standard_normal((n, 3, 4)).astype(np.float32)
   llk, lat = vae.marginal_log_prob(x, n_mcmc=n, reduce=None, eps=eps)
@@ -581,7 +544,7 @@ def test_api_save_load_round_trip(bk, tmp_path, fmt):
   from odin_ai_amd.vae import VAMPRIOR_VARIABLE, VampriorVAE
   L, DEV = bk.L, bk.dev
   vae, u, idx = _vamp_model(L, DEV, K=5)
-  x, eps = _api_case()
+  x, eps = tiny_batch(2)
   vae.optimize(x, eps=eps, learning_rate=1e-2)
   path = str(tmp_path / 'w')
   vae.save_weights(path, save_format=fmt)

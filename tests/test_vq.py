@@ -14,8 +14,9 @@ import torch
 from odin_ai_amd._lib import OdinError
 from odin_ai_amd.engine import RANGE_WORDS, VAEEngine
 from oracle import vae_oracle as vo
+from tests.engine_util import launch_record, tiny_spec
 from tests.range_audit import RangeAudit
-from tests.test_latent_regularizers import _adam_ref, _Hip, api_nets, tiny_spec
+from tests.test_latent_regularizers import _adam_ref, _Hip, api_nets
 from tests.test_vamprior import PLAIN_STEP_CALLS
 from tests.vq_util import VQRef, assign64, bwd64, check_assignment, ema64, near_ties
 
@@ -337,41 +338,10 @@ def test_three_train_steps_follow_float64_adam(bk, ema):
 
 
 # ---- 3. engine behaviour ------------------------------------------------------------------------------------------------
-def _launch_record(bk, steps=1, **kw):
-  """train_steps of a tiny engine; -> (engine, the names of every library call of the LAST step, in order): the
-  recorder of tests/test_vamprior.py"""
-  enc, dec, in_shape, zdim = tiny_spec()
-  calls = []
-  eng = VAEEngine(enc, dec, in_shape, zdim, 4, bk.dev, lib=bk.L, **kw)
-
-  class Rec:
-    def __init__(self, L):
-      self._L = L
-
-    def __getattr__(self, name):
-      fn = getattr(self._L, name)
-      if not name.startswith('odin_'):
-        return fn
-
-      def call(*a):
-        calls.append(name)
-        return fn(*a)
-      return call
-  eng.lib = Rec(bk.L)
-  eng.enc.lib = eng.dec.lib = eng.lib
-  rng = np.random.default_rng(3)
-  x = bk.T(np.clip(rng.random((4,) + in_shape), 1e-6, 1 - 1e-6))
-  eps = bk.T(rng.standard_normal((4, zdim)))
-  for _ in range(steps):
-    calls.clear()
-    eng.train_step(x, eps, lr=1e-3, beta=2.0)
-  return eng, calls
-
-
 def test_plain_engine_call_list_is_unchanged(bk):
-  eng, c1 = _launch_record(bk, vq_codes=None, vq_code_size=8, vq_commitment=3.0, vq_ema=True)
+  eng, c1 = launch_record(bk, vq_codes=None, vq_code_size=8, vq_commitment=3.0, vq_ema=True)
   assert c1 == PLAIN_STEP_CALLS and eng.vq_K is None
-  _, c2 = _launch_record(bk, steps=2)
+  _, c2 = launch_record(bk, steps=2)
   steady = list(PLAIN_STEP_CALLS)
   steady.remove('odin_slab_reduce_sumsq')
   assert c2 == steady
@@ -382,7 +352,7 @@ def test_plain_engine_call_list_is_unchanged(bk):
 
 @pytest.mark.parametrize('ema', [False, True])
 def test_vq_codes_adds_the_two_calls_and_drops_the_latent_ones(bk, ema):
-  eng, c = _launch_record(bk, steps=2, vq_codes=5, vq_code_size=8, vq_ema=ema)
+  eng, c = launch_record(bk, steps=2, vq_codes=5, vq_code_size=8, vq_ema=ema)
   assert c.count('odin_vq_assign') == 1 and c.count('odin_vq_bwd') == 1
   assert not [n for n in c if 'latent' in n or 'neck' in n or 'rng' in n or 'head' in n or 'tail' in n]
   assert c.index('odin_vq_assign') < c.index('odin_elbo_bernoulli_fwd_bwd_ranged') < c.index('odin_vq_bwd')
