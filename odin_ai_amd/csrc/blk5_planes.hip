@@ -459,9 +459,10 @@ __global__ __launch_bounds__(512) void wgrad5_blk_kernel(W5Params p) {
 
 // Conv2D(k, s1, SAME), k = 5 (pads 2, 2) or 4 (pads 1, 2), over CI in {32, 64} reduction channels: forward and data
 // gradient (there CI = the layer's OUTPUT channels, CO its input channels)
-bool odin_conv5_blk_applicable(int B, int H, int W, int CI, int CO, int KH, int KW, int S, int pt, int pl, int center) {
+bool odin_conv5_blk_applicable(const odin_geom& g) {
+  const int B = g.B, H = g.H, W = g.W, CI = g.CI, CO = g.CO, KH = g.KH, KW = g.KW, S = g.S, pt = g.pt, pl = g.pl;
   if (!odin_blk_enabled(2.0 * B * H * W * (double)(KH * KW) * CI * CO)) return false;
-  if (!((KH == 5 || KH == 4) && KW == KH && S == 1 && pt == (KH - 1) / 2 && pl == (KW - 1) / 2 && !center &&
+  if (!((KH == 5 || KH == 4) && KW == KH && S == 1 && pt == (KH - 1) / 2 && pl == (KW - 1) / 2 && !g.center &&
         (CI == 32 || CI == 64) && (CO % 32) == 0))
     return false;
   if (H < 1 || W < 1 || H > 4096 || W > 4096) return false;
@@ -499,9 +500,10 @@ int odin_conv5_blk_launch(const float* in, const float* w, const float* bias, co
 }
 
 // weight gradient of a Conv2D(k, s1), k = 5 or 4: x [B, H, W, CI], dy [B, H, W, CO]
-bool odin_wgrad5_blk_applicable(int B, int H, int W, int CI, int CO, int KH, int KW, int S, int pt, int pl, int center) {
+bool odin_wgrad5_blk_applicable(const odin_geom& g) {
+  const int B = g.B, H = g.H, W = g.W, CI = g.CI, CO = g.CO, KH = g.KH, KW = g.KW, S = g.S, pt = g.pt, pl = g.pl;
   if (!odin_blk_enabled(2.0 * B * H * W * (double)(KH * KW) * CI * CO)) return false;
-  if (!((KH == 5 || KH == 4) && KW == KH && S == 1 && pt == (KH - 1) / 2 && pl == (KW - 1) / 2 && !center &&
+  if (!((KH == 5 || KH == 4) && KW == KH && S == 1 && pt == (KH - 1) / 2 && pl == (KW - 1) / 2 && !g.center &&
         (CI % 32) == 0 && (CO % 32) == 0))
     return false;
   if (H < 1 || W < 1 || H > 4096 || W > 4096) return false;

@@ -318,18 +318,13 @@ bool odin_blk_enabled(double flop) {
 }
 
 // Conv2DTranspose(k4, s2, SAME) forward from CI in {32, 64} channels / Conv2D(k4, s2) data gradient, any H x W
-bool odin_tconv_blk_applicable(int B, int H, int W, int CI, int CO, int KH, int KW, int S, int pt, int pl, int center) {
+bool odin_tconv_blk_applicable(const odin_geom& g) {
+  const int B = g.B, H = g.H, W = g.W, CI = g.CI, CO = g.CO, KH = g.KH, KW = g.KW, S = g.S, pt = g.pt, pl = g.pl;
   if (!odin_blk_enabled(2.0 * B * H * W * 16.0 * CI * CO * blk_scale_for_width(W))) return false;
-  if (!(KH == 4 && KW == 4 && S == 2 && pt == 1 && pl == 1 && !center && (CI == 32 || CI == 64) && (CO % 32) == 0))
+  if (!(KH == 4 && KW == 4 && S == 2 && pt == 1 && pl == 1 && !g.center && (CI == 32 || CI == 64) && (CO % 32) == 0))
     return false;
   if (H < 1 || W < 1 || H > 4096 || W > 4096) return false;
   return (size_t)B * H * W * CI * 4 < 0x7FFF0000ull && (size_t)B * H * W * 4 * CO * 4 < 0x7FFF0000ull;
-}
-
-int odin_tconv_blk_rows(int B, int H, int W, int CO) {
-  const int n_tiles = B * ((H + 7) / 8) * ((W + 7) / 8);
-  const int tpw = tb_tiles_per_wg(n_tiles, CO / 32);
-  return (n_tiles + tpw - 1) / tpw;
 }
 
 // epi 1: forward (bias + act); epi 2: data gradient (x act'(aux), column sums into colsum[rows][CO])
@@ -1035,10 +1030,10 @@ __global__ __launch_bounds__(512) void bwd_blk_kernel(BBParams p) {
 }  // namespace
 
 // Conv2D(k4, s2, SAME) forward over 32 input channels / Conv2DTranspose(k4, s2) data gradient over 32 output channels
-bool odin_fconv_blk_applicable(int B, int H, int W, int CI, int OH, int OW, int CO, int KH, int KW, int S, int pt, int pl,
-                               int center) {
+bool odin_fconv_blk_applicable(const odin_geom& g) {
+  const int B = g.B, H = g.H, W = g.W, CI = g.CI, OH = g.OH, OW = g.OW, CO = g.CO, KH = g.KH, KW = g.KW, S = g.S;
   if (!odin_blk_enabled(2.0 * B * OH * OW * 16.0 * CI * CO * blk_scale_for_width(OW))) return false;
-  if (!(KH == 4 && KW == 4 && S == 2 && pt == 1 && pl == 1 && !center && CI == 32 && (CO % 32) == 0)) return false;
+  if (!(KH == 4 && KW == 4 && S == 2 && g.pt == 1 && g.pl == 1 && !g.center && CI == 32 && (CO % 32) == 0)) return false;
   if (H != 2 * OH || W != 2 * OW || OH < 1 || OW < 1 || H > 8192 || W > 8192) return false;
   return (size_t)B * H * W * CI * 4 < 0x7FFF0000ull && (size_t)B * OH * OW * CO * 4 < 0x7FFF0000ull;
 }
@@ -1072,10 +1067,10 @@ int odin_fconv_blk_launch(const float* in, const float* w, const float* bias, co
 }
 
 // weight gradient of a 4x4 / stride-2 layer: U fine [B, 2 OH, 2 OW, CI], V coarse [B, OH, OW, CO] (names of wgrad_planes.hip)
-bool odin_wgrad_blk_applicable(int B, int H, int W, int CI, int OH, int OW, int CO, int KH, int KW, int S, int pt, int pl,
-                               int center) {
+bool odin_wgrad_blk_applicable(const odin_geom& g) {
+  const int B = g.B, H = g.H, W = g.W, CI = g.CI, OH = g.OH, OW = g.OW, CO = g.CO, KH = g.KH, KW = g.KW, S = g.S;
   if (!odin_blk_enabled(2.0 * B * OH * OW * 16.0 * CI * CO * blk_scale_for_width(OW))) return false;
-  if (!(KH == 4 && KW == 4 && S == 2 && pt == 1 && pl == 1 && !center && (CI % 32) == 0 && (CO % 32) == 0)) return false;
+  if (!(KH == 4 && KW == 4 && S == 2 && g.pt == 1 && g.pl == 1 && !g.center && (CI % 32) == 0 && (CO % 32) == 0)) return false;
   if (H != 2 * OH || W != 2 * OW || OH < 1 || OW < 1 || H > 8192 || W > 8192) return false;
   return (size_t)B * H * W * CI * 4 < 0x7FFF0000ull && (size_t)B * OH * OW * CO * 4 < 0x7FFF0000ull;
 }
@@ -1414,8 +1409,7 @@ __global__ __launch_bounds__(512) void tconv_blk_gtail_kernel(TGParams p) {
 // 1: odin_gaussian_tail_fwd_bwd takes this layer (Conv2DTranspose k4 s2 32 -> 32 + 1x1 head of 2 maps, C = 1)
 extern "C" int odin_gaussian_tail_applicable(const odin_conv_desc* d, int C) {
   return (C == 1 && d->Cin == 32 && d->Cout == 32 && d->OH == 2 * d->H && d->OW == 2 * d->W &&
-          odin_tconv_blk_applicable(d->B, d->H, d->W, d->Cin, d->Cout, d->KH, d->KW, d->stride, d->pad_t, d->pad_l,
-                                    d->center) &&
+          odin_tconv_blk_applicable(odin_geom_fwd(d)) &&
           (size_t)d->B * d->OH * d->OW < 0x3FFF0000ull / 32) ? 1 : 0;
 }
 
@@ -1465,15 +1459,16 @@ extern "C" int odin_gaussian_tail_fwd_bwd(const float* x, const float* w, const 
 }
 
 // the whole backward pass of a Conv2DTranspose(k4, s2) with 32 output channels (x [B, H, W, Cin] -> dy [B, 2H, 2W, 32])
-bool odin_bwd_blk_applicable(int B, int H, int W, int Cin, int Cout) {
+bool odin_bwd_blk_applicable(const odin_geom& g) {
+  const int B = g.B, H = g.H, W = g.W, Cin = g.CI, Cout = g.CO;
   if (!odin_blk_enabled(2.0 * B * H * W * 16.0 * Cin * Cout * blk_scale_for_width(W))) return false;
   if (!(Cout == 32 && (Cin % 32) == 0 && H >= 1 && W >= 1 && H <= 4096 && W <= 4096)) return false;
   return (size_t)B * 4 * H * W * Cout * 4 < 0x7FFF0000ull && (size_t)B * H * W * Cin * 4 < 0x7FFF0000ull;
 }
 
-int odin_bwd_blk_rows(int B, int H, int W, int Cin) {
-  const int n_tiles = B * ((H + 7) / 8) * ((W + 7) / 8);
-  const int tpw = wb_tiles_per_wg(n_tiles, Cin / 32);
+int odin_bwd_blk_rows(const odin_geom& g) {
+  const int n_tiles = g.B * ((g.H + 7) / 8) * ((g.W + 7) / 8);
+  const int tpw = wb_tiles_per_wg(n_tiles, g.CI / 32);
   return (n_tiles + tpw - 1) / tpw;
 }
 

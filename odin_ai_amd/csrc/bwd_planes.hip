@@ -1220,7 +1220,8 @@ int bp_launch(const BPParams& p, dim3 grid, void* stream) {
 }  // namespace
 
 // Conv2DTranspose(k4, s2) with Cout = 32: x [B, H, W, Cin] -> dy [B, 2H, 2W, 32]; aux: ELU activations below
-bool odin_bwd_planes_applicable(int B, int H, int W, int Cin, int Cout) {
+bool odin_bwd_planes_applicable(const odin_geom& g) {
+  const int B = g.B, H = g.H, W = g.W, Cin = g.CI, Cout = g.CO;
   if (odin_blk_first()) return false;   // (diagnostics: odin_debug_blk_first)
   if (odin_exact_fp32() || ODIN_DIAG_ENV("ODIN_NOPLANES") || ODIN_DIAG_ENV("ODIN_NOBWDPLANES")) return false;
   if (!((Cout == 32 || Cout == 64) && (Cin % 32) == 0 && (W == 8 || W == 16 || W == 32) && (H % (32 / W)) == 0)) return false;
@@ -1228,9 +1229,9 @@ bool odin_bwd_planes_applicable(int B, int H, int W, int Cin, int Cout) {
   return bp_tiles_per_wg(W, B * (H / (32 / W)), Cin / 32) > 0;
 }
 
-int odin_bwd_planes_rows(int B, int H, int W, int Cin) {
-  const int n_tiles = B * (H / (32 / W));
-  const int tpw = bp_tiles_per_wg(W, n_tiles, Cin / 32);
+int odin_bwd_planes_rows(const odin_geom& g) {
+  const int n_tiles = g.B * (g.H / (32 / g.W));
+  const int tpw = bp_tiles_per_wg(g.W, n_tiles, g.CI / 32);
   return tpw > 0 ? (n_tiles + tpw - 1) / tpw : 0;
 }
 

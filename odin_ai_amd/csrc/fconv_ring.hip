@@ -416,11 +416,11 @@ int odin_fconv_ring_launch(const float* in, const float* w, const float* bias, c
   return fr_launch_pass(p, epi, true, grid, lds, stream);
 }
 
-bool odin_fconv_ring_applicable(int H, int W, int CI, int OH, int OW, int CO, int KH, int KW, int S,
-                                int pt, int pl, int center) {
+bool odin_fconv_ring_applicable(const odin_geom& g) {
+  const int H = g.H, W = g.W, CI = g.CI, OH = g.OH, OW = g.OW, CO = g.CO, KH = g.KH, KW = g.KW, S = g.S;
   static int off = -1;
   if (off < 0) off = ODIN_DIAG_ENV("ODIN_NOFRING") ? 1 : 0;
-  return !off && KH == 4 && KW == 4 && S == 2 && pt == 1 && pl == 1 && (CI == 32 || CI == 64) &&
-         (CO % 32) == 0 && !center && H == 2 * OH && W == 2 * OW && (OW == 8 || OW == 16 || OW == 32) &&
+  return !off && KH == 4 && KW == 4 && S == 2 && g.pt == 1 && g.pl == 1 && (CI == 32 || CI == 64) &&
+         (CO % 32) == 0 && !g.center && H == 2 * OH && W == 2 * OW && (OW == 8 || OW == 16 || OW == 32) &&
          (OH % (64 / OW)) == 0;
 }

@@ -1586,408 +1586,27 @@ int launch_gather(int mode, GParams& p, void* stream, int max_blocks, int* rows_
 #endif
 }
 
-void fill_common(GParams& p, const odin_conv_desc* d) {
-  memset(&p, 0, sizeof(p));
-  p.B = d->B;
-  p.KH = d->KH;
-  p.KW = d->KW;
-  p.S = d->stride;
-  p.pt = d->pad_t;
-  p.pl = d->pad_l;
-}
-
 }  // namespace
 
 extern "C" int odin_max_slab_rows(void) { return ODIN_MAX_COLSUM_BLOCKS; }
 
-// The forward half of the range contract (include/odin_hip.h: odin_conv_desc.x_amax / y_amax): a layer that is handed
-// a word for its output leaves a valid bound in it -- from the epilogue of the plane / implicit-GEMM / first-layer
-// families, by one pass over y behind the others.
-static int track_y(int rc, const float* y, const odin_conv_desc* d, void* stream) {
-  if (rc != 0 || y == nullptr || d->y_amax == nullptr) return rc;
-  return odin_absmax_fold(y, (size_t)d->B * d->OH * d->OW * d->Cout, d->y_amax, stream);
-}
-
-// ---- Conv2D -------------------------------------------------------------------------
-extern "C" int odin_conv2d_fwd(const float* x, const float* w, const float* bias, float* y,
-                               const odin_conv_desc* d, void* stream) {
-  if (odin_smallc_applicable(d)) return odin_smallc_fwd(x, w, bias, y, d, stream);   // (tracks y itself)
-  if (odin_pw1x1_applicable(d)) return track_y(odin_pw1x1_fwd(x, w, bias, y, d, stream), y, d, stream);
-  if (d->act == ODIN_ACT_ELU && bias != nullptr &&
-      odin_fconv_planes_applicable(d->B, d->H, d->W, d->Cin, d->OH, d->OW, d->Cout, d->KH, d->KW, d->stride,
-                                   d->pad_t, d->pad_l, d->center))
-    return odin_fconv_planes_launch(x, w, bias, nullptr, y, nullptr, nullptr, d->B, d->OH, d->OW, d->Cin, d->Cout,
-                                    1, d->x_amax, d->y_amax, stream);
-  if (d->act == ODIN_ACT_ELU && bias != nullptr &&
-      odin_fconv_ring_applicable(d->H, d->W, d->Cin, d->OH, d->OW, d->Cout, d->KH, d->KW, d->stride,
-                                 d->pad_t, d->pad_l, d->center))
-    return track_y(odin_fconv_ring_launch(x, w, bias, nullptr, y, nullptr, nullptr, d->B, d->H, d->W, d->Cin,
-                                          d->OH, d->OW, d->Cout, 1, stream), y, d, stream);
-  // 5x5 / stride-1 layers (the MNIST conv stack): block windows with the weights in LDS (blk5_planes.hip)
-  if (bias != nullptr && d->H == d->OH && d->W == d->OW &&
-      odin_conv5_blk_applicable(d->B, d->H, d->W, d->Cin, d->Cout, d->KH, d->KW, d->stride, d->pad_t, d->pad_l, d->center))
-    return odin_conv5_blk_launch(x, w, bias, nullptr, y, nullptr, nullptr, d->B, d->H, d->W, d->Cin, d->Cout, d->KH, 1, d->act,
-                                 d->x_amax, d->y_amax, stream);
-  if (bias != nullptr &&
-      odin_fconv_blk_applicable(d->B, d->H, d->W, d->Cin, d->OH, d->OW, d->Cout, d->KH, d->KW, d->stride, d->pad_t,
-                                d->pad_l, d->center))
-    return odin_fconv_blk_launch(x, w, bias, nullptr, y, nullptr, nullptr, d->B, d->OH, d->OW, d->Cin, d->Cout, 1,
-                                 d->act, d->x_amax, d->y_amax, stream);
-  if (odin_igemm_h_applicable(0, d->B, d->H, d->W, d->Cin, d->OH, d->OW, d->Cout, d->KH, d->KW, d->stride, d->center))
-    return odin_igemm_h_launch(0, x, w, bias, nullptr, 0, y, nullptr, d->B, d->H, d->W, d->Cin, d->OH, d->OW,
-                               d->Cout, d->KH, d->KW, d->stride, d->pad_t, d->pad_l, d->act, d->x_amax, 0, d->y_amax,
-                               stream);
-  if (odin_igemm_applicable(0, d->B, d->H, d->W, d->Cin, d->OH, d->OW, d->Cout, d->KH, d->KW, d->stride,
-                            d->center))
-    return odin_igemm_launch(0, x, w, bias, nullptr, 0, y, nullptr, d->B, d->H, d->W, d->Cin, d->OH, d->OW,
-                             d->Cout, d->KH, d->KW, d->stride, d->pad_t, d->pad_l, d->act, d->y_amax, stream);
-  GParams p;
-  fill_common(p, d);
-  p.in = x; p.w = w; p.bias = bias; p.out = y;
-  p.H = d->H; p.W = d->W; p.CI = d->Cin; p.OH = d->OH; p.OW = d->OW; p.CO = d->Cout;
-  p.wmode = 0; p.act = d->act; p.center = d->center;
-  return track_y(launch_gather(MODE_F, p, stream, odin_num_cus()), y, d, stream);
-}
-
-// dx[b,ih,iw,ci] = sum_{kh,kw,co} dy[b,(ih+pt-kh)/S,(iw+pl-kw)/S,co] * W[kh,kw,ci,co];
-// optionally multiplied by act'(aux) (aux = this layer's input = previous layer's output)
-// THE CONTRACT: a data gradient that is handed a word (d->dx_amax) leaves a valid bound of dx in it, whatever kernel
-// family ran.  The plane / implicit-GEMM families fold max|dx| in from their epilogues (free); every other family
-// (generic gather, 1x1 stream kernel, the fp32 ring kernels) is followed by ONE absmax pass over dx here.  Round 4
-// left those words untouched and told the caller through the *_keeps_range predicates below -- a predicate that
-// disagreed with the dispatch (a column-sum slab sends a layer of > 16384 tiles to the generic kernel) handed the
-// consumers a ZERO word: they scaled by 2^115 and overflowed.  The predicates remain as "kept without an extra pass".
-static int track_dx(int rc, const float* dx, const odin_conv_desc* d, void* stream) {
-  if (rc != 0 || dx == nullptr || d->dx_amax == nullptr) return rc;
-  return odin_absmax_fold(dx, (size_t)d->B * d->H * d->W * d->Cin, d->dx_amax, stream);
-}
-
-// 1: the data gradient of this layer (as dispatched for `aux_act`, with the aux tensor present and NO column-sum slab
-// beyond ODIN_MAX_COLSUM_BLOCKS tiles) folds max|dx| into d->dx_amax in its own epilogue; 0: by a pass of its own
-extern "C" int odin_conv2d_dgrad_keeps_range(const odin_conv_desc* d, int aux_act) {
-  if (odin_pw1x1_applicable(d)) return 0;
-  if (aux_act == ODIN_ACT_ELU && d->H == 2 * d->OH && d->W == 2 * d->OW &&
-      odin_tconv_planes_applicable(d->B, d->OH, d->OW, d->Cout, d->Cin, d->KH, d->KW, d->stride, d->pad_t,
-                                   d->pad_l, 0, 2, 1))
-    return 1;
-  if (aux_act == ODIN_ACT_ELU && d->H == 2 * d->OH && d->W == 2 * d->OW &&
-      odin_tconv_ring_applicable(d->OH, d->OW, d->Cout, d->Cin, d->KH, d->KW, d->stride, d->pad_t, d->pad_l, 0))
-    return 0;
-  if (d->H == 2 * d->OH && d->W == 2 * d->OW &&
-      odin_tconv_blk_applicable(d->B, d->OH, d->OW, d->Cout, d->Cin, d->KH, d->KW, d->stride, d->pad_t, d->pad_l, 0))
-    return 1;
-  if (d->H == d->OH && d->W == d->OW &&
-      odin_conv5_blk_applicable(d->B, d->H, d->W, d->Cout, d->Cin, d->KH, d->KW, d->stride, d->pad_t, d->pad_l, 0))
-    return 1;
-  if (odin_igemm_h_applicable(1, d->B, d->OH, d->OW, d->Cout, d->H, d->W, d->Cin, d->KH, d->KW, d->stride, 0)) return 1;
-  return odin_igemm_applicable(1, d->B, d->OH, d->OW, d->Cout, d->H, d->W, d->Cin, d->KH, d->KW, d->stride, 0) ? 1 : 0;
-}
-extern "C" int odin_deconv2d_dgrad_keeps_range(const odin_conv_desc* d, int aux_act) {
-  if (odin_smalldeconv_applicable(d)) return 1;
-  if (aux_act == ODIN_ACT_ELU &&
-      odin_fconv_planes_applicable(d->B, d->OH, d->OW, d->Cout, d->H, d->W, d->Cin, d->KH, d->KW, d->stride,
-                                   d->pad_t, d->pad_l, 0))
-    return 1;
-  if (odin_fconv_blk_applicable(d->B, d->OH, d->OW, d->Cout, d->H, d->W, d->Cin, d->KH, d->KW, d->stride, d->pad_t,
-                                d->pad_l, 0))
-    return 1;
-  if (odin_igemm_h_applicable(0, d->B, d->OH, d->OW, d->Cout, d->H, d->W, d->Cin, d->KH, d->KW, d->stride, 0)) return 1;
-  const bool ring_two_pass_vs_igemm =
-      d->Cout == 64 && odin_igemm_applicable(0, d->B, d->OH, d->OW, d->Cout, d->H, d->W, d->Cin, d->KH, d->KW,
-                                             d->stride, 0) &&
-      odin_igemm_tiles(0, d->B, d->H, d->W, d->stride) <= ODIN_MAX_COLSUM_BLOCKS;
-  if (!ring_two_pass_vs_igemm && aux_act == ODIN_ACT_ELU &&
-      odin_fconv_ring_applicable(d->OH, d->OW, d->Cout, d->H, d->W, d->Cin, d->KH, d->KW, d->stride, d->pad_t,
-                                 d->pad_l, 0))
-    return 0;
-  return odin_igemm_applicable(0, d->B, d->OH, d->OW, d->Cout, d->H, d->W, d->Cin, d->KH, d->KW, d->stride, 0) ? 1 : 0;
-}
-// 1: the fused tail folds max|g_out| into d->dy_amax itself
-extern "C" int odin_bernoulli_tail_keeps_range(int is_deconv, const odin_conv_desc* d, int C1) {
-  return (is_deconv && d->act == ODIN_ACT_ELU && d->OH == 2 * d->H && d->OW == 2 * d->W &&
-          odin_tconv_planes_applicable(d->B, d->H, d->W, d->Cin, d->Cout, d->KH, d->KW, d->stride, d->pad_t,
-                                       d->pad_l, d->center, 3, C1)) ? 1 : 0;
-}
-
-extern "C" int odin_conv2d_dgrad(const float* dy, const float* w, const float* aux, int aux_act,
-                                 float* dx, float* colsum_slab, int* slab_rows_out,
-                                 const odin_conv_desc* d, void* stream) {
-  if (odin_pw1x1_applicable(d))
-    return track_dx(odin_pw1x1_dgrad(dy, w, aux, aux_act, dx, colsum_slab, slab_rows_out, d, stream), dx, d, stream);
-  // data gradient of a Conv2D = transposed gather over dY: input (OH, OW, Cout), output (H, W, Cin)
-  if (aux_act == ODIN_ACT_ELU && (aux != nullptr || dx == nullptr) && d->H == 2 * d->OH &&
-      d->W == 2 * d->OW &&
-      odin_tconv_planes_applicable(d->B, d->OH, d->OW, d->Cout, d->Cin, d->KH, d->KW, d->stride, d->pad_t,
-                                   d->pad_l, 0, 2, 1))
-    return odin_tconv_planes_launch(dy, w, nullptr, aux, dx, colsum_slab, slab_rows_out, nullptr, nullptr,
-                                    nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1, d->B, d->OH,
-                                    d->OW, d->Cout, d->Cin, 2, d->dy_amax, d->dx_amax, stream);
-  if (aux_act == ODIN_ACT_ELU && (aux != nullptr || dx == nullptr) && d->H == 2 * d->OH &&
-      d->W == 2 * d->OW &&
-      odin_tconv_ring_applicable(d->OH, d->OW, d->Cout, d->Cin, d->KH, d->KW, d->stride, d->pad_t,
-                                 d->pad_l, 0))
-    return track_dx(odin_tconv_ring_launch(dy, w, nullptr, aux, dx, colsum_slab, slab_rows_out, nullptr, nullptr,
-                                           nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1, d->B, d->OH,
-                                           d->OW, d->Cin, 2, stream), dx, d, stream);
-  if (d->H == d->OH && d->W == d->OW &&
-      odin_conv5_blk_applicable(d->B, d->H, d->W, d->Cout, d->Cin, d->KH, d->KW, d->stride, d->pad_t, d->pad_l, 0))
-    return odin_conv5_blk_launch(dy, w, nullptr, aux_act != 0 ? aux : nullptr, dx, colsum_slab, slab_rows_out, d->B,
-                                 d->H, d->W, d->Cout, d->Cin, d->KH, 2, aux_act, d->dy_amax, d->dx_amax, stream);
-  // any other image size: 8 x 8 blocks of dy through LDS windows (blk_planes.hip)
-  if (d->H == 2 * d->OH && d->W == 2 * d->OW &&
-      odin_tconv_blk_applicable(d->B, d->OH, d->OW, d->Cout, d->Cin, d->KH, d->KW, d->stride, d->pad_t, d->pad_l, 0))
-    return odin_tconv_blk_launch(dy, w, nullptr, aux_act != 0 ? aux : nullptr, dx, colsum_slab, slab_rows_out, d->B,
-                                 d->OH, d->OW, d->Cout, d->Cin, 2, aux_act, d->dy_amax, d->dx_amax, stream);
-  if (odin_igemm_h_applicable(1, d->B, d->OH, d->OW, d->Cout, d->H, d->W, d->Cin, d->KH, d->KW, d->stride, 0)) {
-    if (slab_rows_out) *slab_rows_out = odin_igemm_h_rows(1, d->B, d->H, d->W, d->stride);
-    if (dx == nullptr) return 0;  // dry run
-    return odin_igemm_h_launch(1, dy, w, nullptr, aux, aux_act, dx, colsum_slab, d->B, d->OH, d->OW, d->Cout, d->H,
-                               d->W, d->Cin, d->KH, d->KW, d->stride, d->pad_t, d->pad_l, 0, d->dy_amax, 1,
-                               d->dx_amax, stream);
-  }
-  if (odin_igemm_applicable(1, d->B, d->OH, d->OW, d->Cout, d->H, d->W, d->Cin, d->KH, d->KW, d->stride, 0) &&
-      (odin_igemm_tiles(1, d->B, d->H, d->W, d->stride) <= ODIN_MAX_COLSUM_BLOCKS ||
-       (colsum_slab == nullptr && dx != nullptr))) {
-    if (slab_rows_out) *slab_rows_out = odin_igemm_tiles(1, d->B, d->H, d->W, d->stride);
-    if (dx == nullptr) return 0;  // dry run
-    return odin_igemm_launch(1, dy, w, nullptr, aux, aux_act, dx, colsum_slab, d->B, d->OH, d->OW, d->Cout,
-                             d->H, d->W, d->Cin, d->KH, d->KW, d->stride, d->pad_t, d->pad_l, 0, d->dx_amax, stream);
-  }
-  GParams p;
-  fill_common(p, d);
-  p.in = dy; p.w = w; p.out = dx; p.aux = aux; p.aux_act = aux_act; p.colsum_slab = colsum_slab;
-  p.H = d->OH; p.W = d->OW; p.CI = d->Cout; p.OH = d->H; p.OW = d->W; p.CO = d->Cin;
-  p.wmode = 1;
-  return track_dx(launch_gather(MODE_T, p, stream, colsum_slab ? -ODIN_MAX_COLSUM_BLOCKS : odin_num_cus(),
-                                slab_rows_out), dx, d, stream);
-}
-
-// ---- Conv2DTranspose (desc: H,W,Cin = input; OH=H*S, OW=W*S, Cout = output; pads = the
-// SAME pads of the forward conv on the OUTPUT size) ------------------------------------
-extern "C" int odin_deconv2d_fwd(const float* x, const float* w, const float* bias, float* y,
-                                 const odin_conv_desc* d, void* stream) {
-  if (bias != nullptr && odin_smalldeconv_applicable(d)) return odin_smalldeconv_fwd(x, w, bias, y, d, stream);
-  if (d->act == ODIN_ACT_ELU && bias != nullptr && d->OH == 2 * d->H && d->OW == 2 * d->W &&
-      odin_tconv_planes_applicable(d->B, d->H, d->W, d->Cin, d->Cout, d->KH, d->KW, d->stride, d->pad_t,
-                                   d->pad_l, d->center, 1, 1))
-    return odin_tconv_planes_launch(x, w, bias, nullptr, y, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                    nullptr, nullptr, nullptr, nullptr, nullptr, 1, d->B, d->H, d->W,
-                                    d->Cin, d->Cout, 1, d->x_amax, d->y_amax, stream);
-  if (d->act == ODIN_ACT_ELU && bias != nullptr && d->OH == 2 * d->H && d->OW == 2 * d->W &&
-      odin_tconv_ring_applicable(d->H, d->W, d->Cin, d->Cout, d->KH, d->KW, d->stride, d->pad_t,
-                                 d->pad_l, d->center))
-    return track_y(odin_tconv_ring_launch(x, w, bias, nullptr, y, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                          nullptr, nullptr, nullptr, nullptr, nullptr, 1, d->B, d->H, d->W,
-                                          d->Cout, 1, stream), y, d, stream);
-  // a thin small image the implicit-GEMM families cannot take (fewer than 8 channels: MNIST's first deconvolution)
-  if (bias != nullptr && (d->Cin & 7) != 0 && odin_smalldeconv_gen_applicable(d))
-    return odin_smalldeconv_gen_fwd(x, w, bias, y, d, stream);
-  if (bias != nullptr && d->OH == 2 * d->H && d->OW == 2 * d->W &&
-      odin_tconv_blk_applicable(d->B, d->H, d->W, d->Cin, d->Cout, d->KH, d->KW, d->stride, d->pad_t, d->pad_l, d->center))
-    return odin_tconv_blk_launch(x, w, bias, nullptr, y, nullptr, nullptr, d->B, d->H, d->W, d->Cin, d->Cout, 1, d->act,
-                                 d->x_amax, d->y_amax, stream);
-  if (odin_igemm_h_applicable(1, d->B, d->H, d->W, d->Cin, d->OH, d->OW, d->Cout, d->KH, d->KW, d->stride, d->center))
-    return odin_igemm_h_launch(1, x, w, bias, nullptr, 0, y, nullptr, d->B, d->H, d->W, d->Cin, d->OH, d->OW,
-                               d->Cout, d->KH, d->KW, d->stride, d->pad_t, d->pad_l, d->act, d->x_amax, 0, d->y_amax,
-                               stream);
-  if (odin_igemm_applicable(1, d->B, d->H, d->W, d->Cin, d->OH, d->OW, d->Cout, d->KH, d->KW, d->stride,
-                            d->center))
-    return odin_igemm_launch(1, x, w, bias, nullptr, 0, y, nullptr, d->B, d->H, d->W, d->Cin, d->OH, d->OW,
-                             d->Cout, d->KH, d->KW, d->stride, d->pad_t, d->pad_l, d->act, d->y_amax, stream);
-  GParams p;
-  fill_common(p, d);
-  p.in = x; p.w = w; p.bias = bias; p.out = y;
-  p.H = d->H; p.W = d->W; p.CI = d->Cin; p.OH = d->OH; p.OW = d->OW; p.CO = d->Cout;
-  p.wmode = 1; p.act = d->act; p.center = d->center;
-  return track_y(launch_gather(MODE_T, p, stream, odin_num_cus()), y, d, stream);
-}
-
-extern "C" int odin_deconv2d_dgrad(const float* dy, const float* w, const float* aux,
-                                   int aux_act, float* dx, float* colsum_slab,
-                                   int* slab_rows_out, const odin_conv_desc* d, void* stream) {
-  // data gradient of a Conv2DTranspose = strided gather over dY: input (OH, OW, Cout), output (H, W, Cin)
-  if (colsum_slab == nullptr && odin_smalldeconv_applicable(d)) {
-    if (slab_rows_out) *slab_rows_out = 0;
-    if (dx == nullptr) return 0;  // dry run
-    return odin_smalldeconv_bwd(nullptr, dy, w, aux, aux_act, dx, nullptr, nullptr, d, stream);
-  }
-  if (aux_act == ODIN_ACT_ELU && (aux != nullptr || dx == nullptr) &&
-      odin_fconv_planes_applicable(d->B, d->OH, d->OW, d->Cout, d->H, d->W, d->Cin, d->KH, d->KW, d->stride,
-                                   d->pad_t, d->pad_l, 0))
-    return odin_fconv_planes_launch(dy, w, nullptr, aux, dx, colsum_slab, slab_rows_out, d->B, d->H, d->W,
-                                    d->Cout, d->Cin, 2, d->dy_amax, d->dx_amax, stream);
-  if (odin_fconv_blk_applicable(d->B, d->OH, d->OW, d->Cout, d->H, d->W, d->Cin, d->KH, d->KW, d->stride, d->pad_t,
-                                d->pad_l, 0))
-    return odin_fconv_blk_launch(dy, w, nullptr, aux_act != 0 ? aux : nullptr, dx, colsum_slab, slab_rows_out, d->B, d->H,
-                                 d->W, d->Cout, d->Cin, 2, aux_act, d->dy_amax, d->dx_amax, stream);
-  if (odin_igemm_h_applicable(0, d->B, d->OH, d->OW, d->Cout, d->H, d->W, d->Cin, d->KH, d->KW, d->stride, 0)) {
-    if (slab_rows_out) *slab_rows_out = odin_igemm_h_rows(0, d->B, d->H, d->W, d->stride);
-    if (dx == nullptr) return 0;  // dry run
-    return odin_igemm_h_launch(0, dy, w, nullptr, aux, aux_act, dx, colsum_slab, d->B, d->OH, d->OW, d->Cout, d->H,
-                               d->W, d->Cin, d->KH, d->KW, d->stride, d->pad_t, d->pad_l, 0, d->dy_amax, 1,
-                               d->dx_amax, stream);
-  }
-  // (64 reduction channels take two fconv_ring passes: where the implicit-GEMM kernel covers the layer it does the
-  // same work in one launch -- decoder2 of the dSprites stack: 30.8 us in two launches vs 30.2 us in one)
-  const bool ring_two_pass_vs_igemm =
-      d->Cout == 64 && odin_igemm_applicable(0, d->B, d->OH, d->OW, d->Cout, d->H, d->W, d->Cin, d->KH, d->KW,
-                                             d->stride, 0) &&
-      odin_igemm_tiles(0, d->B, d->H, d->W, d->stride) <= ODIN_MAX_COLSUM_BLOCKS;
-  if (!ring_two_pass_vs_igemm && aux_act == ODIN_ACT_ELU && (aux != nullptr || dx == nullptr) &&
-      odin_fconv_ring_applicable(d->OH, d->OW, d->Cout, d->H, d->W, d->Cin, d->KH, d->KW, d->stride,
-                                 d->pad_t, d->pad_l, 0))
-    return track_dx(odin_fconv_ring_launch(dy, w, nullptr, aux, dx, colsum_slab, slab_rows_out, d->B, d->OH,
-                                           d->OW, d->Cout, d->H, d->W, d->Cin, 2, stream), dx, d, stream);
-  if (odin_igemm_applicable(0, d->B, d->OH, d->OW, d->Cout, d->H, d->W, d->Cin, d->KH, d->KW, d->stride, 0) &&
-      (odin_igemm_tiles(0, d->B, d->H, d->W, d->stride) <= ODIN_MAX_COLSUM_BLOCKS ||
-       (colsum_slab == nullptr && dx != nullptr))) {
-    if (slab_rows_out) *slab_rows_out = odin_igemm_tiles(0, d->B, d->H, d->W, d->stride);
-    if (dx == nullptr) return 0;  // dry run
-    return odin_igemm_launch(0, dy, w, nullptr, aux, aux_act, dx, colsum_slab, d->B, d->OH, d->OW, d->Cout,
-                             d->H, d->W, d->Cin, d->KH, d->KW, d->stride, d->pad_t, d->pad_l, 0, d->dx_amax, stream);
-  }
-  GParams p;
-  fill_common(p, d);
-  p.in = dy; p.w = w; p.out = dx; p.aux = aux; p.aux_act = aux_act; p.colsum_slab = colsum_slab;
-  p.H = d->OH; p.W = d->OW; p.CI = d->Cout; p.OH = d->H; p.OW = d->W; p.CO = d->Cin;
-  p.wmode = 0;
-  return track_dx(launch_gather(MODE_F, p, stream, colsum_slab ? -ODIN_MAX_COLSUM_BLOCKS : odin_num_cus(),
-                                slab_rows_out), dx, d, stream);
-}
-
-// Dense layers whose reduction width is a multiple of 8 through the implicit-GEMM kernel (a 1x1 convolution on a
-// 1x1 image; FactorVAE's 1000-unit discriminator, the 512-unit default nets; enc4 of the dSprites step:
-// 12.6 + 9.2 + 7.7 -> 9.9 + 9.6 + 6.4 us stand-alone, 11 us per step in the graph); ODIN_NODENSEIGEMM: A/B switch
-static bool dense_via_igemm() { return ODIN_DIAG_ENV("ODIN_NODENSEIGEMM") == nullptr; }
-
-// ---- Dense: y[B,N] = act(x[B,K] @ w[K,N] + b) ----------------------------------------
-extern "C" int odin_dense_fwd(const float* x, const float* w, const float* bias, float* y, int B,
-                              int K, int N, int act, void* stream) {
-  return odin_dense_fwd_ranged(x, w, bias, y, B, K, N, act, nullptr, nullptr, stream);
-}
-
-// the same with the activation range words (include/odin_hip.h: the range contract): x_amax is read by the two-plane
-// GEMM, y_amax is valid on return whatever family ran
-extern "C" int odin_dense_fwd_ranged(const float* x, const float* w, const float* bias, float* y, int B, int K, int N,
-                                     int act, const uint32_t* x_amax, uint32_t* y_amax, void* stream) {
-  auto fold = [&](int rc) {
-    if (rc != 0 || y == nullptr || y_amax == nullptr) return rc;
-    return odin_absmax_fold(y, (size_t)B * N, y_amax, stream);
-  };
-  if (odin_tiny_dense_ok(B, K, N)) return fold(odin_tiny_dense_fwd(x, w, bias, y, B, K, N, act, stream));
-  // one thin side (FactorVAE's first / last discriminator layers): streaming kernels, range word kept by the kernel
-  if (odin_thin_dense_kind(B, K, N) != 0 && ((((size_t)x | (size_t)w | (size_t)y | (size_t)bias)) & 15) == 0)
-    return odin_thin_dense_fwd(x, w, bias, y, B, K, N, act, y_amax, stream);
-  if (odin_dense_h_ok(B, K, N)) return odin_dense_h_fwd(x, w, bias, y, B, K, N, act, x_amax, y_amax, stream);
-  if (dense_via_igemm() && odin_igemm_applicable(0, B, 1, 1, K, 1, 1, N, 1, 1, 1, 0))
-    return odin_igemm_launch(0, x, w, bias, nullptr, 0, y, nullptr, B, 1, 1, K, 1, 1, N, 1, 1, 1, 0, 0, act, y_amax,
-                             stream);
-  if (odin_dense_gemm_ok(B, K, N)) return fold(odin_dense_gemm_fwd(x, w, bias, y, B, K, N, act, stream));
+// the generic tiled gather: what every chain of dispatch.hip ends in (odin_internal.h)
+int odin_gather_generic(int mode_t, int wmode, const odin_geom& g, const float* in, const float* w, const float* bias,
+                        int act, const float* aux, int aux_act, float* out, float* colsum_slab, int max_blocks,
+                        int* rows_out, const odin_tail_args* tail, int* n_part_out, void* stream) {
   GParams p;
   memset(&p, 0, sizeof(p));
-  p.in = x; p.w = w; p.bias = bias; p.out = y;
-  p.B = B; p.H = 1; p.W = 1; p.CI = K; p.OH = 1; p.OW = 1; p.CO = N;
-  p.KH = p.KW = 1; p.S = 1; p.act = act; p.wmode = 0;
-  return fold(launch_gather(MODE_F, p, stream, odin_num_cus()));
-}
-
-// dx[B,K] = (dy[B,N] @ w[K,N]^T) * act'(aux)
-extern "C" int odin_dense_dgrad(const float* dy, const float* w, const float* aux, int aux_act,
-                                float* dx, float* colsum_slab, int* slab_rows_out, int B, int K,
-                                int N, void* stream) {
-  // (no range words through this entry: a plane GEMM bounds dy itself)
-  return odin_dense_dgrad_ranged(dy, w, aux, aux_act, dx, colsum_slab, slab_rows_out, B, K, N, nullptr, nullptr,
-                                 stream);
-}
-
-// the kernel families below (without a column-sum slab) that fold max|dx| into dx_amax
-bool odin_dense_dgrad_tracks(int B, int K, int N) {
-  if (odin_tiny_dense_ok(B, K, N)) return false;
-  return odin_thin_dense_kind(B, K, N) != 0 || odin_dense_h_ok(B, K, N) || (dense_via_igemm() && odin_igemm_applicable(1, B, 1, 1, N, 1, 1, K, 1, 1, 1, 0)) ||
-         odin_dense_gemm_ok(B, K, N);
-}
-
-int odin_dense_dgrad_ranged(const float* dy, const float* w, const float* aux, int aux_act, float* dx,
-                            float* colsum_slab, int* slab_rows_out, int B, int K, int N, const uint32_t* dy_amax,
-                            uint32_t* dx_amax, void* stream) {
-  // (the same contract as the convolutions' track_dx: a word that is handed in is valid on return)
-  auto fold = [&](int rc) {
-    if (rc != 0 || dx == nullptr || dx_amax == nullptr) return rc;
-    return odin_absmax_fold(dx, (size_t)B * K, dx_amax, stream);
-  };
-  if (odin_tiny_dense_ok(B, K, N))
-    return fold(odin_tiny_dense_dgrad(dy, w, aux, aux_act, dx, colsum_slab, slab_rows_out, B, K, N, stream));
-  if (colsum_slab == nullptr && odin_thin_dense_kind(B, K, N) != 0 &&
-      ((((size_t)dy | (size_t)w | (size_t)dx | (size_t)aux)) & 15) == 0) {
-    if (slab_rows_out) *slab_rows_out = 0;
-    if (dx == nullptr) return 0;
-    return odin_thin_dense_dgrad(dy, w, aux, aux_act, dx, B, K, N, dx_amax, stream);
-  }
-  if (colsum_slab == nullptr && odin_dense_h_ok(B, K, N)) {
-    if (slab_rows_out) *slab_rows_out = 0;
-    if (dx == nullptr) return 0;
-    return odin_dense_h_dgrad(dy, w, aux, aux_act, dx, B, K, N, dy_amax, dx_amax, stream);
-  }
-  // (as a transposed 1x1 gather: reduction over the N outputs, weights [k_in][n] with n contiguous)
-  if (colsum_slab == nullptr && dense_via_igemm() && odin_igemm_applicable(1, B, 1, 1, N, 1, 1, K, 1, 1, 1, 0)) {
-    if (slab_rows_out) *slab_rows_out = 0;
-    if (dx == nullptr) return 0;
-    return odin_igemm_launch(1, dy, w, nullptr, aux, aux_act, dx, nullptr, B, 1, 1, N, 1, 1, K, 1, 1, 1, 0, 0, 0,
-                             dx_amax, stream);
-  }
-  if (colsum_slab == nullptr && odin_dense_gemm_ok(B, K, N)) {
-    if (slab_rows_out) *slab_rows_out = 0;
-    if (dx == nullptr) return 0;
-    return odin_dense_gemm_dgrad(dy, w, aux, aux_act, dx, B, K, N, dx_amax, stream);
-  }
-  GParams p;
-  memset(&p, 0, sizeof(p));
-  p.in = dy; p.w = w; p.out = dx; p.aux = aux; p.aux_act = aux_act; p.colsum_slab = colsum_slab;
-  p.B = B; p.H = 1; p.W = 1; p.CI = N; p.OH = 1; p.OW = 1; p.CO = K;
-  p.KH = p.KW = 1; p.S = 1; p.wmode = 1;
-  return fold(launch_gather(MODE_F, p, stream, colsum_slab ? -ODIN_MAX_COLSUM_BLOCKS : odin_num_cus(),
-                            slab_rows_out));
-}
-
-// ---- fused decoder tail: (Conv2DTranspose | Conv2D)(act) -> Conv2D 1x1 linear (C1<=4 maps)
-// -> Independent(Bernoulli).log_prob(target), forward + backward in one launch ----------
-extern "C" int odin_bernoulli_tail_fwd_bwd(int is_deconv, const float* x, const float* w,
-                                           const float* bias, const float* w1, const float* b1,
-                                           const float* target, float* logits, float* g_out,
-                                           float* llk_part, int* n_part_out, float* tail_slab,
-                                           int* slab_rows_out, const float* scale,
-                                           const odin_conv_desc* d, int C1, void* stream) {
-  // (the range contract: a word handed in as d->dy_amax bounds g_out on return -- the plane kernel folds it in from
-  // its epilogue, the other families are followed by one pass)
-  auto tail_fold = [&](int rc) {
-    if (rc != 0 || g_out == nullptr || d->dy_amax == nullptr) return rc;
-    return odin_absmax_fold(g_out, (size_t)d->B * d->OH * d->OW * d->Cout, d->dy_amax, stream);
-  };
-  if (is_deconv && d->act == ODIN_ACT_ELU && d->OH == 2 * d->H && d->OW == 2 * d->W &&
-      odin_tconv_planes_applicable(d->B, d->H, d->W, d->Cin, d->Cout, d->KH, d->KW, d->stride, d->pad_t,
-                                   d->pad_l, d->center, 3, C1))
-    return odin_tconv_planes_launch(x, w, bias, nullptr, g_out, nullptr, slab_rows_out, w1, b1, target,
-                                    logits, llk_part, n_part_out, tail_slab, scale, C1, d->B, d->H, d->W,
-                                    d->Cin, d->Cout, 3, d->x_amax, d->dy_amax, stream);
-  if (is_deconv && d->act == ODIN_ACT_ELU && d->Cout == 32 && (C1 == 1 || C1 == 3) &&
-      d->OH == 2 * d->H && d->OW == 2 * d->W &&
-      odin_tconv_ring_applicable(d->H, d->W, d->Cin, d->Cout, d->KH, d->KW, d->stride, d->pad_t,
-                                 d->pad_l, d->center))
-    return tail_fold(odin_tconv_ring_launch(x, w, bias, nullptr, g_out, nullptr, slab_rows_out, w1, b1, target,
-                                            logits, llk_part, n_part_out, tail_slab, scale, C1, d->B, d->H, d->W,
-                                            d->Cout, 3, stream));
-  GParams p;
-  fill_common(p, d);
-  p.in = x; p.w = w; p.bias = bias; p.out = g_out;
-  p.H = d->H; p.W = d->W; p.CI = d->Cin; p.OH = d->OH; p.OW = d->OW; p.CO = d->Cout;
-  p.wmode = is_deconv ? 1 : 0; p.act = d->act; p.center = d->center;
+  p.in = in; p.w = w; p.bias = bias; p.out = out; p.aux = aux; p.aux_act = aux_act; p.colsum_slab = colsum_slab;
+  p.B = g.B; p.H = g.H; p.W = g.W; p.CI = g.CI; p.OH = g.OH; p.OW = g.OW; p.CO = g.CO;
+  p.KH = g.KH; p.KW = g.KW; p.S = g.S; p.pt = g.pt; p.pl = g.pl;
+  p.wmode = wmode; p.act = act; p.center = g.center;
+  if (tail == nullptr) return launch_gather(mode_t ? MODE_T : MODE_F, p, stream, max_blocks, rows_out);
   TailParams tp;
-  tp.w1 = w1; tp.b1 = b1; tp.target = target; tp.logits = logits; tp.llk_part = llk_part;
-  tp.slab = tail_slab; tp.scale = scale; tp.C1 = C1;
-  int rc = launch_gather(is_deconv ? MODE_T : MODE_F, p, stream, -ODIN_MAX_COLSUM_BLOCKS,
-                         slab_rows_out, &tp);
+  tp.w1 = tail->w1; tp.b1 = tail->b1; tp.target = tail->target; tp.logits = tail->logits; tp.llk_part = tail->llk_part;
+  tp.slab = tail->slab; tp.scale = tail->scale; tp.C1 = tail->C1;
+  const int rc = launch_gather(mode_t ? MODE_T : MODE_F, p, stream, max_blocks, rows_out, &tp);
   if (n_part_out) *n_part_out = p.OH / (p.TR > 0 ? p.TR : 1);  // log-likelihood parts per sample
-  return tail_fold(rc);
+  return rc;
 }
 
 // diagnostics: device buffer (>= 64 int64) receiving s_memtime stamps of workgroup 0

@@ -507,9 +507,9 @@ void odin_igemm_set_stamps(void* buf) { g_ig_stamps = (long long*)buf; }
 // 25 taps, strides 1 / 2 (transposed gathers: output extents divisible by the stride), <= 1.2 GFLOP, and
 // tensors below 2^29 elements (32-bit byte offsets).  `tmode`: transposed gather.  (H, W, CI) = gathered
 // tensor, (OH, OW, CO) = produced tensor.
-bool odin_igemm_applicable(int tmode, int B, int H, int W, int CI, int OH, int OW, int CO, int KH, int KW,
-                           int S, int center) {
-  if (!igemm_enabled() || center) return false;
+bool odin_igemm_applicable(int tmode, const odin_geom& g) {
+  const int B = g.B, H = g.H, W = g.W, CI = g.CI, OH = g.OH, OW = g.OW, CO = g.CO, KH = g.KH, KW = g.KW, S = g.S;
+  if (!igemm_enabled() || g.center) return false;
   if (CI < 8 || (CI & 7) != 0 || CI > 8192 || KH * KW > 25 || KH < 1 || KW < 1 || KH > 8 || KW > 8 || S < 1 || S > 2)
     return false;
   if (tmode && (OH % S || OW % S || KH < S || KW < S)) return false;
@@ -523,9 +523,9 @@ bool odin_igemm_applicable(int tmode, int B, int H, int W, int CI, int OH, int O
 }
 
 // rows of column sums the data-gradient launch writes (= its 32-row tiles)
-int odin_igemm_tiles(int tmode, int B, int OH, int OW, int S) {
-  const int SS = tmode ? S : 1;
-  const int Mc = B * (OH / SS) * (OW / SS);
+int odin_igemm_tiles(int tmode, const odin_geom& g) {
+  const int SS = tmode ? g.S : 1;
+  const int Mc = g.B * (g.OH / SS) * (g.OW / SS);
   return SS * SS * ((Mc + 31) / 32);
 }
 
@@ -564,9 +564,9 @@ int odin_igemm_launch(int tmode, const float* in, const float* w, const float* b
 }
 
 // weight gradient: fine tensor (FH, FW, CU) gathered around the pixels of the coarse one (h, w, CV)
-bool odin_igemm_wgrad_applicable(int B, int FH, int FW, int CU, int h, int w, int CV, int KH, int KW, int S,
-                                 int center) {
-  if (!igemm_enabled() || center) return false;
+bool odin_igemm_wgrad_applicable(const odin_geom& g) {
+  const int B = g.B, FH = g.H, FW = g.W, CU = g.CI, h = g.OH, w = g.OW, CV = g.CO, KH = g.KH, KW = g.KW, S = g.S;
+  if (!igemm_enabled() || g.center) return false;
   if (CU < 8 || (CU & 7) != 0 || CU > 8192 || KH * KW > 64 || KH < 1 || KW < 1 || S < 1 || S > 4) return false;
   if (FH > 8192 || FW > 8192 || (long)B * h * w > 65536) return false;
   if ((double)KH * KW * CU * CU >= 4e9) return false;  // exactness of the magic-number row decoding
@@ -577,9 +577,9 @@ bool odin_igemm_wgrad_applicable(int B, int FH, int FW, int CU, int h, int w, in
 }
 
 // reduction splits (= slab rows) of the weight-gradient launch
-int odin_igemm_wgrad_rows(int B, int h, int w, int KH, int KW, int CU, int CV) {
-  const int M = B * h * w;
-  const long tiles = (long)((KH * KW * CU + 31) / 32) * ((CV + 31) / 32);
+int odin_igemm_wgrad_rows(const odin_geom& g) {
+  const int M = g.B * g.OH * g.OW;
+  const long tiles = (long)((g.KH * g.KW * g.CI + 31) / 32) * ((g.CO + 31) / 32);
   int R = (M + IW_CHUNK - 1) / IW_CHUNK;
   // enough workgroups to fill the chip, at least 64 pixels each
   while (tiles * R < 512 && M / (R * 2) >= 64 && R * 2 <= ODIN_MAX_SLAB_BLOCKS) R *= 2;
@@ -600,7 +600,7 @@ int odin_igemm_wgrad_launch(const float* u, const float* v, float* slab, int sla
   p.KH = KH; p.KW = KW; p.S = S; p.pt = pt; p.pl = pl;
   p.mg_cu = CU <= 1 ? 0u : (unsigned)(((1L << 32) + CU - 1) / CU);
   p.M = B * h * w; p.want_bias = want_bias;
-  const int R = odin_igemm_wgrad_rows(B, h, w, KH, KW, CU, CV);
+  const int R = odin_igemm_wgrad_rows(odin_geom{B, FH, FW, CU, h, w, CV, KH, KW, S, pt, pl, 0});
   p.chunk = (((p.M + R - 1) / R) + 7) & ~7;
   if (p.chunk > IW_CHUNK) return odin_fail(-2, "igemm wgrad: reduction chunk too long");
   dim3 grid((CV + 31) / 32, (KH * KW * CU + 31) / 32, R);

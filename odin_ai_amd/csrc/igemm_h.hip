@@ -705,9 +705,9 @@ extern "C" double odin_debug_igemm_h_min_flop(double flop) {
 
 // forward / data gradient: 16-channel steps, at least 128 tiles (fewer: the fp32 kernel splits the reduction of a tile
 // over the waves of a workgroup, igemm.hip)
-bool odin_igemm_h_applicable(int tmode, int B, int H, int W, int CI, int OH, int OW, int CO, int KH, int KW, int S,
-                             int center) {
-  if (!ih_enabled() || center) return false;
+bool odin_igemm_h_applicable(int tmode, const odin_geom& g) {
+  const int B = g.B, H = g.H, W = g.W, CI = g.CI, OH = g.OH, OW = g.OW, CO = g.CO, KH = g.KH, KW = g.KW, S = g.S;
+  if (!ih_enabled() || g.center) return false;
   if (CI < 16 || (CI & 15) != 0 || CI > 8192 || KH * KW > 25 || KH < 1 || KW < 1 || KH > 8 || KW > 8 || S < 1 || S > 2)
     return false;
   if (tmode && (OH % S || OW % S || KH < S || KW < S)) return false;
@@ -727,9 +727,9 @@ bool odin_igemm_h_applicable(int tmode, int B, int H, int W, int CI, int OH, int
 }
 
 // rows of column sums the data-gradient launch writes (= its gridDim.y)
-int odin_igemm_h_rows(int tmode, int B, int OH, int OW, int S) {
-  const int SS = tmode ? S : 1;
-  const long Mc = (long)B * (OH / SS) * (OW / SS);
+int odin_igemm_h_rows(int tmode, const odin_geom& g) {
+  const int SS = tmode ? g.S : 1;
+  const long Mc = (long)g.B * (g.OH / SS) * (g.OW / SS);
   const long ntile = (long)SS * SS * ((Mc + 31) / 32);
   long gy = (ntile + IH_NW - 1) / IH_NW;
   if (gy > ODIN_MAX_COLSUM_BLOCKS) gy = ODIN_MAX_COLSUM_BLOCKS;
@@ -837,9 +837,9 @@ int odin_igemm_h_launch(int tmode, const float* in, const float* w, const float*
 }
 
 // weight gradient: fine tensor (FH, FW, CU) gathered around the pixels of the coarse one (h, w, CV)
-bool odin_igemm_h_wgrad_applicable(int B, int FH, int FW, int CU, int h, int w, int CV, int KH, int KW, int S,
-                                   int center) {
-  if (!ih_enabled() || center) return false;
+bool odin_igemm_h_wgrad_applicable(const odin_geom& g) {
+  const int B = g.B, FH = g.H, FW = g.W, CU = g.CI, h = g.OH, w = g.OW, CV = g.CO, KH = g.KH, KW = g.KW, S = g.S;
+  if (!ih_enabled() || g.center) return false;
   if (CU < 8 || (CU & 7) != 0 || CU > 8192 || KH * KW > 30 || KH < 1 || KW < 1 || KW > 8 || S < 1 || S > 4) return false;
   if (FH > 8192 || FW > 8192) return false;
   const long M = (long)B * h * w;
@@ -851,9 +851,9 @@ bool odin_igemm_h_wgrad_applicable(int B, int FH, int FW, int CU, int h, int w, 
 }
 
 // reduction splits (= slab rows) of the weight-gradient launch
-int odin_igemm_h_wgrad_rows(int B, int h, int w, int KH, int KW, int CU, int CV) {
-  const int M = B * h * w;
-  const long tiles = (long)((KH * KW * CU + 31) / 32) * ((CV + 31) / 32);
+int odin_igemm_h_wgrad_rows(const odin_geom& g) {
+  const int M = g.B * g.OH * g.OW;
+  const long tiles = (long)((g.KH * g.KW * g.CI + 31) / 32) * ((g.CO + 31) / 32);
   int R = (M + IHW_CHUNK - 17) / (IHW_CHUNK - 16);
   // enough workgroups to fill the chip twice, at least 128 pixels each
   while (tiles * R < 2048 && M / (R * 2) >= 128 && R * 2 <= ODIN_MAX_SLAB_BLOCKS) R *= 2;
@@ -869,7 +869,7 @@ int odin_igemm_h_wgrad_launch(const float* u, const float* v, float* slab, int s
   p.B = B; p.FH = FH; p.FW = FW; p.CU = CU; p.h = h; p.w = w; p.CV = CV;
   p.KH = KH; p.KW = KW; p.S = S; p.pt = pt; p.pl = pl; p.want_bias = want_bias;
   p.M = B * h * w;
-  const int R = odin_igemm_h_wgrad_rows(B, h, w, KH, KW, CU, CV);
+  const int R = odin_igemm_h_wgrad_rows(odin_geom{B, FH, FW, CU, h, w, CV, KH, KW, S, pt, pl, 0});
   p.chunk = (((p.M + R - 1) / R) + 15) & ~15;
   if (p.chunk > IHW_CHUNK) return odin_fail(-2, "igemm_h wgrad: chunk beyond the pixel table");
   const float* g = grad_u ? u : v;

@@ -139,7 +139,7 @@ extern "C" int odin_absmax(const float* t, size_t n, uint32_t* word, void* strea
 static std::atomic<int> g_absmax_fallbacks{0};
 extern "C" int odin_debug_absmax_fallbacks(void) { return g_absmax_fallbacks.load(); }
 
-// producer side of the range contract (gather_conv.hip: track_dx): a kernel family that does not track its outputs
+// producer side of the range contract (dispatch.hip: keep_range): a kernel family that does not track its outputs
 // is followed by one pass that folds max|t| into the caller's word (atomicMax: the word keeps what it already holds)
 int odin_absmax_fold(const float* t, size_t n, uint32_t* word, void* stream) {
   ++g_absmax_fallbacks;

@@ -681,12 +681,12 @@ __global__ __launch_bounds__(NW * 64) void smallc_wgrad_mfma_kernel(SCParams p) 
 
 }  // namespace
 
-bool odin_smallc_applicable(const odin_conv_desc* d) {
-  const int K = d->KH * d->KW * d->Cin;
-  if ((long)d->B * d->OH * d->OW * d->Cout >= (1L << 29)) return false;  // byte offsets fit 31 bits
-  if ((long)d->B * d->H * d->W * d->Cin >= (1L << 29)) return false;
-  return d->Cin <= 4 && (d->Cout % 4) == 0 && d->Cout <= 64 && (K == 16 || K == 25 || K == 48) &&
-         (size_t)16 * (K + 1) * d->Cout * 4 <= 150 * 1024;
+bool odin_smallc_applicable(const odin_geom& g) {
+  const int K = g.KH * g.KW * g.CI;
+  if ((long)g.B * g.OH * g.OW * g.CO >= (1L << 29)) return false;  // byte offsets fit 31 bits
+  if ((long)g.B * g.H * g.W * g.CI >= (1L << 29)) return false;
+  return g.CI <= 4 && (g.CO % 4) == 0 && g.CO <= 64 && (K == 16 || K == 25 || K == 48) &&
+         (size_t)16 * (K + 1) * g.CO * 4 <= 150 * 1024;
 }
 
 static bool g_sc_planes = true;

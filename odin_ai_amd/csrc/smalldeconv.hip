@@ -324,23 +324,23 @@ void sd_fill(SDParams& p, const odin_conv_desc* d) {
 
 // Conv2DTranspose 4x4 / stride 2 / SAME pads (1, 1), Cin in {8, 16}, Cout = 64, at most 64 input pixels; the exact-fp32
 // switch keeps it (it IS exact fp32)
-bool odin_smalldeconv_applicable(const odin_conv_desc* d) {
+bool odin_smalldeconv_applicable(const odin_geom& g) {
   if (ODIN_DIAG_ENV("ODIN_NOSMALLDECONV")) return false;
-  if (d->KH != 4 || d->KW != 4 || d->stride != 2 || d->pad_t != 1 || d->pad_l != 1 || d->center) return false;
-  if (d->Cout != SD_C1 || (d->Cin != 8 && d->Cin != 16) || d->OH != 2 * d->H || d->OW != 2 * d->W) return false;
-  if (d->H < 1 || d->W < 1 || d->H * d->W > 64) return false;
-  if ((long)d->B * d->OH * d->OW * d->Cout >= (1L << 29)) return false;
-  return sd_bwd_lds(sd_samples(d->B), d->H, d->W, d->Cin) <= 150 * 1024;
+  if (g.KH != 4 || g.KW != 4 || g.S != 2 || g.pt != 1 || g.pl != 1 || g.center) return false;
+  if (g.CO != SD_C1 || (g.CI != 8 && g.CI != 16) || g.OH != 2 * g.H || g.OW != 2 * g.W) return false;
+  if (g.H < 1 || g.W < 1 || g.H * g.W > 64) return false;
+  if ((long)g.B * g.OH * g.OW * g.CO >= (1L << 29)) return false;
+  return sd_bwd_lds(sd_samples(g.B), g.H, g.W, g.CI) <= 150 * 1024;
 }
 
 // the generic forward: Conv2DTranspose(64, k <= 5, stride 2, SAME) from a thin small image
-bool odin_smalldeconv_gen_applicable(const odin_conv_desc* d) {
+bool odin_smalldeconv_gen_applicable(const odin_geom& g) {
   if (ODIN_DIAG_ENV("ODIN_NOSMALLDECONV")) return false;
-  if (d->KH != d->KW || d->KH < 2 || d->KH > 5 || d->stride != 2 || d->center) return false;
-  if (d->Cout != SD_C1 || (d->Cin & 3) != 0 || d->Cin < 4 || d->Cin > 16 || d->OH != 2 * d->H || d->OW != 2 * d->W) return false;
-  if (d->H < 1 || d->W < 1 || d->H * d->W > 64 || d->B > 65535) return false;
-  if ((long)d->B * d->OH * d->OW * d->Cout >= (1L << 29)) return false;
-  return (size_t)(d->KH * d->KW * SD_C1 * d->Cin + d->H * d->W * d->Cin) * 4 <= 120 * 1024;
+  if (g.KH != g.KW || g.KH < 2 || g.KH > 5 || g.S != 2 || g.center) return false;
+  if (g.CO != SD_C1 || (g.CI & 3) != 0 || g.CI < 4 || g.CI > 16 || g.OH != 2 * g.H || g.OW != 2 * g.W) return false;
+  if (g.H < 1 || g.W < 1 || g.H * g.W > 64 || g.B > 65535) return false;
+  if ((long)g.B * g.OH * g.OW * g.CO >= (1L << 29)) return false;
+  return (size_t)(g.KH * g.KW * SD_C1 * g.CI + g.H * g.W * g.CI) * 4 <= 120 * 1024;
 }
 int odin_smalldeconv_gen_fwd(const float* x, const float* w, const float* bias, float* y, const odin_conv_desc* d,
                              void* stream) {
@@ -355,9 +355,9 @@ int odin_smalldeconv_gen_fwd(const float* x, const float* w, const float* bias, 
   return odin_check_launch("smalldeconv_gen_fwd");
 }
 
-int odin_smalldeconv_rows(const odin_conv_desc* d) {
-  const int S = sd_samples(d->B);
-  return (d->B + S - 1) / S;
+static int odin_smalldeconv_rows(const odin_geom& g) {
+  const int S = sd_samples(g.B);
+  return (g.B + S - 1) / S;
 }
 
 int odin_smalldeconv_fwd(const float* x, const float* w, const float* bias, float* y, const odin_conv_desc* d,
@@ -366,7 +366,7 @@ int odin_smalldeconv_fwd(const float* x, const float* w, const float* bias, floa
   sd_fill(p, d);
   p.x = x; p.w = w; p.bias = bias; p.y = y; p.y_amax = d->y_amax;
   p.w_al = (((size_t)w) & 15) == 0;
-  const int rows = odin_smalldeconv_rows(d);
+  const int rows = odin_smalldeconv_rows(odin_geom_fwd(d));
   const size_t lds = (size_t)p.S * (d->H + 2) * (d->W + 2) * d->Cin * 4;
   if (d->Cin == 8) ODIN_LAUNCH((smalldeconv_fwd_kernel<8>), dim3(rows), dim3(SD_NT), lds, stream, p);
   else ODIN_LAUNCH((smalldeconv_fwd_kernel<16>), dim3(rows), dim3(SD_NT), lds, stream, p);
@@ -376,7 +376,7 @@ int odin_smalldeconv_fwd(const float* x, const float* w, const float* bias, floa
 // either half may be left out (dx == NULL / slab == NULL); a dry run (both NULL) only reports the slab rows
 int odin_smalldeconv_bwd(const float* x, const float* dy, const float* w, const float* aux, int aux_act, float* dx,
                          float* slab, int* rows_out, const odin_conv_desc* d, void* stream) {
-  const int rows = odin_smalldeconv_rows(d);
+  const int rows = odin_smalldeconv_rows(odin_geom_fwd(d));
   if (rows_out) *rows_out = rows;
   if (dx == nullptr && slab == nullptr) return 0;
   if ((((size_t)dy | (size_t)slab) & 15) != 0) return odin_fail(-2, "smalldeconv: dy / slab must be 16-byte aligned");

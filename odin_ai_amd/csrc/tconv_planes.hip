@@ -965,14 +965,14 @@ static long long* g_tp_stamps = nullptr;
 void odin_tconv_planes_set_stamps(void* buf) { g_tp_stamps = (long long*)buf; }
 
 // ODIN_SPLIT (any value) and ODIN_NOPLANES select the older instances (gather_conv.hip)
-bool odin_tconv_planes_applicable(int B, int H, int W, int CI, int CO, int KH, int KW, int S, int pt,
-                                  int pl, int center, int epi, int C1) {
+bool odin_tconv_planes_applicable(const odin_geom& g, int epi, int C1) {
+  const int B = g.B, H = g.H, W = g.W, CI = g.CI, CO = g.CO, KH = g.KH, KW = g.KW, S = g.S, pt = g.pt, pl = g.pl;
   if (odin_blk_first()) return false;   // (diagnostics: odin_debug_blk_first)
   // (read per call: the A/B tests switch paths inside one process; a captured graph never comes here)
   if (odin_exact_fp32() || ODIN_DIAG_ENV("ODIN_NOPLANES") || ODIN_DIAG_ENV("ODIN_SPLIT")) return false;
   if (epi == 3 && (CO != 32 || (C1 != 1 && C1 != 3) || CI != 32 || W == 8)) return false;
   return KH == 4 && KW == 4 && S == 2 && pt == 1 && pl == 1 && (CI == 32 || CI == 64) && (CO % 32) == 0 &&
-         !center && (W == 8 || W == 16 || W == 32) && (H % (64 / W)) == 0 && (size_t)B * H * W * CI * 4 < (1ull << 31) &&
+         !g.center && (W == 8 || W == 16 || W == 32) && (H % (64 / W)) == 0 && (size_t)B * H * W * CI * 4 < (1ull << 31) &&
          (size_t)B * H * W * 4 * C1 * 4 < (1ull << 31) && tp_tiles_per_wg(W, B * (H / (64 / W)), CO / 32) > 0;
 }
 

@@ -27,7 +27,7 @@
 // the diagnostics build (`make diag`) and absent from the product library.
 #ifndef ODIN_DIAG
 void odin_tconv_ring_set_stamps(void*) {}
-bool odin_tconv_ring_applicable(int, int, int, int, int, int, int, int, int, int) { return false; }
+bool odin_tconv_ring_applicable(const odin_geom&) { return false; }
 int odin_tconv_ring_launch(const float*, const float*, const float*, const float*, float*, float*, int*, const float*,
                            const float*, const float*, float*, float*, int*, float*, const float*, int, int, int, int,
                            int, int, void*) {
@@ -532,8 +532,8 @@ __global__ __launch_bounds__(TR_THREADS) void tconv_ring_kernel(TRParams p) {
 static long long* g_tr_stamps = nullptr;
 void odin_tconv_ring_set_stamps(void* buf) { g_tr_stamps = (long long*)buf; }
 
-bool odin_tconv_ring_applicable(int H, int W, int CI, int CO, int KH, int KW, int S, int pt, int pl,
-                                int center) {
+bool odin_tconv_ring_applicable(const odin_geom& g) {
+  const int H = g.H, W = g.W, CI = g.CI, CO = g.CO, KH = g.KH, KW = g.KW, S = g.S, pt = g.pt, pl = g.pl;
   // Opt-in (ODIN_TRING=1): measured on MI355X this all-fp32 form is not faster than the bf16-plane
   // instances of gather_conv.hip (fused tail 105 vs 90 us, encoder1 data gradient 25.7 vs 25.5 us):
   // v_mfma_f32_*_f32 shares the vector ALU's issue with every other VALU instruction (nothing of an
@@ -541,7 +541,7 @@ bool odin_tconv_ring_applicable(int H, int W, int CI, int CO, int KH, int KW, in
   const char* e = ODIN_DIAG_ENV("ODIN_TRING");
   if (e == nullptr || e[0] != '1') return false;
   return KH == 4 && KW == 4 && S == 2 && pt == 1 && pl == 1 && CI == 32 && (CO % 32) == 0 &&
-         !center && (W == 16 || W == 32) && (H % (64 / W)) == 0;
+         !g.center && (W == 16 || W == 32) && (H % (64 / W)) == 0;
 }
 
 // epi 1 / 2 as above; epi 3: fused tail with C1 (1 or 3) logit maps

@@ -46,8 +46,8 @@ struct WParams {
   int flat, n_batches;  // Dense: IN tile is one contiguous [NIMG, CIB] block
   long long* stamps;
   int bias_mode;  // 0 none, 1 extra MFMA tile with A = 1, 2 summed while staging DY
-  const uint32_t* g_amax;  // range word of the gradient operand (wgrad_planes only; may be null)
-  const uint32_t* a_amax;  // range word of the activation operand (plane kernels; may be null)
+  const uint32_t* g_amax;  // (never set: the plane families that read range words have Params of their own; the two
+  const uint32_t* a_amax;  //  words stay because WParams is a kernel argument and the device code is left as it is)
 };
 
 // ---- staging ------------------------------------------------------------------------
@@ -1035,29 +1035,6 @@ int launch_wgrad(WParams& p, int* rows_out, void* stream) {
   int gx, gy, gz;
   size_t lds;
   p.slab_stride = p.KH * p.KW * p.CI * p.CO + (p.want_bias ? p.CO : 0);
-  if (odin_wgrad_planes_applicable(p.B, p.H, p.W, p.CI, p.OH, p.OW, p.CO, p.KH, p.KW, p.S, p.pt, p.pl,
-                                   p.center))
-    return odin_wgrad_planes_launch(p.in, p.dy, p.slab, rows_out, p.B, p.OH, p.OW, p.CI, p.CO,
-                                    p.want_bias, p.want_bias ? 0 : 1, p.g_amax, p.a_amax, stream);
-  if (p.H == p.OH && p.W == p.OW && p.want_bias &&
-      odin_wgrad5_blk_applicable(p.B, p.H, p.W, p.CI, p.CO, p.KH, p.KW, p.S, p.pt, p.pl, p.center))
-    return odin_wgrad5_blk_launch(p.in, p.dy, p.slab, rows_out, p.B, p.H, p.W, p.CI, p.CO, p.KH, p.want_bias, p.g_amax,
-                                  p.a_amax, stream);
-  if (odin_wgrad_blk_applicable(p.B, p.H, p.W, p.CI, p.OH, p.OW, p.CO, p.KH, p.KW, p.S, p.pt, p.pl, p.center))
-    return odin_wgrad_blk_launch(p.in, p.dy, p.slab, rows_out, p.B, p.OH, p.OW, p.CI, p.CO, p.want_bias,
-                                 p.want_bias ? 0 : 1, p.g_amax, p.a_amax, stream);
-  if (odin_igemm_h_wgrad_applicable(p.B, p.H, p.W, p.CI, p.OH, p.OW, p.CO, p.KH, p.KW, p.S, p.center)) {
-    if (rows_out) *rows_out = odin_igemm_h_wgrad_rows(p.B, p.OH, p.OW, p.KH, p.KW, p.CI, p.CO);
-    if (p.slab == nullptr) return 0;  // dry run
-    return odin_igemm_h_wgrad_launch(p.in, p.dy, p.slab, p.slab_stride, p.B, p.H, p.W, p.CI, p.OH, p.OW, p.CO,
-                                     p.KH, p.KW, p.S, p.pt, p.pl, p.want_bias, p.want_bias ? 0 : 1, p.g_amax, p.a_amax, stream);
-  }
-  if (odin_igemm_wgrad_applicable(p.B, p.H, p.W, p.CI, p.OH, p.OW, p.CO, p.KH, p.KW, p.S, p.center)) {
-    if (rows_out) *rows_out = odin_igemm_wgrad_rows(p.B, p.OH, p.OW, p.KH, p.KW, p.CI, p.CO);
-    if (p.slab == nullptr) return 0;  // dry run
-    return odin_igemm_wgrad_launch(p.in, p.dy, p.slab, p.slab_stride, p.B, p.H, p.W, p.CI, p.OH, p.OW, p.CO,
-                                   p.KH, p.KW, p.S, p.pt, p.pl, p.want_bias, stream);
-  }
   {
     const int rc = try_launch_ws(p, rows_out, stream);
     if (rc != 1) return rc;
@@ -1294,221 +1271,17 @@ __global__ __launch_bounds__(256) void slab_reduce_kernel(ReduceJobs jobs) {
 
 }  // namespace
 
-extern "C" int odin_conv2d_wgrad(const float* x, const float* dy, float* slab,
-                                 int* slab_rows_out, const odin_conv_desc* d, void* stream) {
-  if (odin_smallc_applicable(d)) return odin_smallc_wgrad(x, dy, slab, slab_rows_out, d, stream);
-  if (odin_pw1x1_applicable(d)) return odin_pw1x1_wgrad(x, dy, slab, slab_rows_out, d, stream);
+// the generic tiled weight gradient: what the weight-gradient chains of dispatch.hip end in (odin_internal.h)
+int odin_wgrad_generic(const odin_geom& g, const float* in, const float* dy, float* slab, int want_bias, int* rows_out,
+                       void* stream) {
   WParams p;
   memset(&p, 0, sizeof(p));
-  p.in = x; p.dy = dy; p.slab = slab;
-  p.B = d->B; p.H = d->H; p.W = d->W; p.CI = d->Cin; p.OH = d->OH; p.OW = d->OW; p.CO = d->Cout;
-  p.KH = d->KH; p.KW = d->KW; p.S = d->stride; p.pt = d->pad_t; p.pl = d->pad_l;
-  p.center = d->center; p.want_bias = 1;
-  p.g_amax = d->dy_amax;
-  p.a_amax = d->x_amax;
-  return launch_wgrad(p, slab_rows_out, stream);
+  p.in = in; p.dy = dy; p.slab = slab;
+  p.B = g.B; p.H = g.H; p.W = g.W; p.CI = g.CI; p.OH = g.OH; p.OW = g.OW; p.CO = g.CO;
+  p.KH = g.KH; p.KW = g.KW; p.S = g.S; p.pt = g.pt; p.pl = g.pl;
+  p.center = g.center; p.want_bias = want_bias;
+  return launch_wgrad(p, rows_out, stream);
 }
-
-// x = deconv input [B,H,W,Cin], dy = grad wrt deconv pre-activation output [B,OH,OW,Cout]
-extern "C" int odin_deconv2d_wgrad(const float* x, const float* dy, float* slab,
-                                   int* slab_rows_out, const odin_conv_desc* d, void* stream) {
-  if (odin_smalldeconv_applicable(d))   // (dry run: slab == NULL only reports the rows)
-    return odin_smalldeconv_bwd(x, dy, nullptr, nullptr, 0, nullptr, slab, slab_rows_out, d, stream);
-  WParams p;
-  memset(&p, 0, sizeof(p));
-  p.in = dy; p.dy = x; p.slab = slab;
-  p.B = d->B; p.H = d->OH; p.W = d->OW; p.CI = d->Cout; p.OH = d->H; p.OW = d->W; p.CO = d->Cin;
-  p.KH = d->KH; p.KW = d->KW; p.S = d->stride; p.pt = d->pad_t; p.pl = d->pad_l;
-  p.center = 0; p.want_bias = 0;
-  p.g_amax = d->dy_amax;
-  p.a_amax = d->x_amax;
-  return launch_wgrad(p, slab_rows_out, stream);
-}
-
-// 1: some launch of this layer (forward or weight gradient, as dispatched now) is a two-plane kernel that READS the
-// range word of the layer input (odin_conv_desc.x_amax) -- a caller uses it to decide whether the layer below is asked
-// to keep that word at all (a wrong answer is harmless: a plane kernel without a word carries x unscaled, as in round 4)
-extern "C" int odin_conv2d_reads_x_range(const odin_conv_desc* d) {
-  if (odin_smallc_applicable(d) || odin_pw1x1_applicable(d)) return 0;
-  return (odin_fconv_planes_applicable(d->B, d->H, d->W, d->Cin, d->OH, d->OW, d->Cout, d->KH, d->KW, d->stride,
-                                       d->pad_t, d->pad_l, d->center) ||
-          odin_igemm_h_applicable(0, d->B, d->H, d->W, d->Cin, d->OH, d->OW, d->Cout, d->KH, d->KW, d->stride, d->center) ||
-          odin_fconv_blk_applicable(d->B, d->H, d->W, d->Cin, d->OH, d->OW, d->Cout, d->KH, d->KW, d->stride, d->pad_t,
-                                    d->pad_l, d->center) ||
-          (d->H == d->OH && d->W == d->OW &&
-           (odin_conv5_blk_applicable(d->B, d->H, d->W, d->Cin, d->Cout, d->KH, d->KW, d->stride, d->pad_t, d->pad_l,
-                                      d->center) ||
-            odin_wgrad5_blk_applicable(d->B, d->H, d->W, d->Cin, d->Cout, d->KH, d->KW, d->stride, d->pad_t, d->pad_l,
-                                       d->center))) ||
-          odin_wgrad_blk_applicable(d->B, d->H, d->W, d->Cin, d->OH, d->OW, d->Cout, d->KH, d->KW, d->stride, d->pad_t,
-                                    d->pad_l, d->center) ||
-          odin_wgrad_planes_applicable(d->B, d->H, d->W, d->Cin, d->OH, d->OW, d->Cout, d->KH, d->KW, d->stride,
-                                       d->pad_t, d->pad_l, d->center) ||
-          odin_igemm_h_wgrad_applicable(d->B, d->H, d->W, d->Cin, d->OH, d->OW, d->Cout, d->KH, d->KW, d->stride,
-                                        d->center)) ? 1 : 0;
-}
-extern "C" int odin_deconv2d_reads_x_range(const odin_conv_desc* d) {
-  return ((d->OH == 2 * d->H && d->OW == 2 * d->W &&
-           odin_tconv_planes_applicable(d->B, d->H, d->W, d->Cin, d->Cout, d->KH, d->KW, d->stride, d->pad_t, d->pad_l,
-                                        d->center, 1, 1)) ||
-          (d->OH == 2 * d->H && d->OW == 2 * d->W &&
-           odin_tconv_blk_applicable(d->B, d->H, d->W, d->Cin, d->Cout, d->KH, d->KW, d->stride, d->pad_t, d->pad_l,
-                                     d->center)) ||
-          odin_igemm_h_applicable(1, d->B, d->H, d->W, d->Cin, d->OH, d->OW, d->Cout, d->KH, d->KW, d->stride, d->center) ||
-          odin_wgrad_planes_applicable(d->B, d->OH, d->OW, d->Cout, d->H, d->W, d->Cin, d->KH, d->KW, d->stride,
-                                       d->pad_t, d->pad_l, 0) ||
-          odin_wgrad_blk_applicable(d->B, d->OH, d->OW, d->Cout, d->H, d->W, d->Cin, d->KH, d->KW, d->stride, d->pad_t,
-                                    d->pad_l, 0) ||
-          odin_igemm_h_wgrad_applicable(d->B, d->OH, d->OW, d->Cout, d->H, d->W, d->Cin, d->KH, d->KW, d->stride, 0))
-             ? 1 : 0;
-}
-extern "C" int odin_dense_reads_x_range(int B, int K, int N) { return odin_dense_h_ok(B, K, N) ? 1 : 0; }
-
-extern "C" int odin_dense_wgrad(const float* x, const float* dy, float* slab, int* slab_rows_out,
-                                int B, int K, int N, void* stream) {
-  if (odin_dense_h_ok(B, K, N)) {  // both widths >= 256: the two-plane GEMM, ONE complete slab row
-    if (slab_rows_out) *slab_rows_out = 1;
-    if (slab == nullptr) return 0;  // dry run
-    return odin_dense_h_wgrad(x, dy, slab, B, K, N, nullptr, nullptr, stream);
-  }
-  if (odin_thin_dense_wgrad_rows(B, K, N) > 0 && (slab == nullptr || ((((size_t)x | (size_t)dy | (size_t)slab)) & 15) == 0)) {
-    // one thin side: streaming kernel, slab rows = row chunks of the batch (a dry run cannot see the pointers: callers
-    // allocate at least 16-byte aligned tensors)
-    if (slab_rows_out) *slab_rows_out = odin_thin_dense_wgrad_rows(B, K, N);
-    if (slab == nullptr) return 0;  // dry run
-    return odin_thin_dense_wgrad(x, dy, slab, B, K, N, stream);
-  }
-  // (also the tiny layers: their forward / data gradient run on the vector ALUs, but the weight gradient
-  // through the generic kernel was a 14.5 us launch for 0.001 GFLOP)
-  if (!ODIN_DIAG_ENV("ODIN_NODENSEIGEMM") && !odin_tiny_dense_ok(B, K, N) &&
-      odin_igemm_wgrad_applicable(B, 1, 1, K, 1, 1, N, 1, 1, 1, 0)) {
-    if (slab_rows_out) *slab_rows_out = odin_igemm_wgrad_rows(B, 1, 1, 1, 1, K, N);
-    if (slab == nullptr) return 0;  // dry run
-    return odin_igemm_wgrad_launch(x, dy, slab, K * N + N, B, 1, 1, K, 1, 1, N, 1, 1, 1, 0, 0, 1, stream);
-  }
-  if (odin_dense_gemm_ok(B, K, N) && !ODIN_DIAG_ENV("ODIN_NOTINYWGRADGEMM")) {
-    // small GEMM: the waves of a workgroup split the batch, the result is complete: ONE slab row
-    if (slab_rows_out) *slab_rows_out = 1;
-    if (slab == nullptr) return 0;  // dry run
-    return odin_dense_gemm_wgrad(x, dy, slab, B, K, N, stream);
-  }
-  WParams p;
-  memset(&p, 0, sizeof(p));
-  p.in = x; p.dy = dy; p.slab = slab;
-  p.B = B; p.H = 1; p.W = 1; p.CI = K; p.OH = 1; p.OW = 1; p.CO = N;
-  p.KH = p.KW = 1; p.S = 1; p.want_bias = 1;
-  return launch_wgrad(p, slab_rows_out, stream);
-}
-
-// ---- a layer's whole backward pass in one call: weight gradient + data gradient.  Where both run on the
-// implicit-GEMM kernels (igemm.hip) they share ONE launch; otherwise exactly the two calls above. ----
-extern "C" int odin_conv2d_bwd(const float* x, const float* dy, const float* w, const float* aux, int aux_act,
-                               float* dx, float* colsum_slab, int* colsum_rows_out, float* wslab,
-                               int* wslab_rows_out, const odin_conv_desc* d, void* stream) {
-  odin_igemm_pair_begin();
-  int rc = odin_conv2d_wgrad(x, dy, wslab, wslab_rows_out, d, stream);
-  if (rc == 0) rc = odin_conv2d_dgrad(dy, w, aux, aux_act, dx, colsum_slab, colsum_rows_out, d, stream);
-  const int rc2 = odin_igemm_pair_end();
-  return rc != 0 ? rc : rc2;
-}
-
-extern "C" int odin_deconv2d_bwd(const float* x, const float* dy, const float* w, const float* aux, int aux_act,
-                                 float* dx, float* colsum_slab, int* colsum_rows_out, float* wslab,
-                                 int* wslab_rows_out, const odin_conv_desc* d, void* stream) {
-  if (colsum_slab == nullptr && dx != nullptr && wslab != nullptr && odin_smalldeconv_applicable(d)) {
-    // the decoders' first Conv2DTranspose: weight and data gradient in ONE launch that stages dy once (smalldeconv.hip)
-    if (colsum_rows_out) *colsum_rows_out = 0;
-    return odin_smalldeconv_bwd(x, dy, w, aux, aux_act, dx, wslab, wslab_rows_out, d, stream);
-  }
-  // (a dry run -- dx == NULL and wslab == NULL -- reports the rows of the ONE-call form: with 64 output channels the
-  // fused launch writes more slab rows than odin_deconv2d_wgrad alone; callers size their slab for both)
-  const bool dry = dx == nullptr && wslab == nullptr;
-  if (((dx != nullptr && wslab != nullptr && aux != nullptr) || dry) && aux_act == ODIN_ACT_ELU && d->KH == 4 &&
-      d->KW == 4 && d->stride == 2 && d->pad_t == 1 && d->pad_l == 1 && d->OH == 2 * d->H && d->OW == 2 * d->W &&
-      odin_bwd_planes_applicable(d->B, d->H, d->W, d->Cin, d->Cout) &&
-      odin_wgrad_planes_applicable(d->B, d->OH, d->OW, d->Cout, d->H, d->W, d->Cin, d->KH, d->KW, d->stride, d->pad_t,
-                                   d->pad_l, 0) &&
-      odin_fconv_planes_applicable(d->B, d->OH, d->OW, d->Cout, d->H, d->W, d->Cin, d->KH, d->KW, d->stride, d->pad_t,
-                                   d->pad_l, 0)) {
-    // dy is fetched, scaled and split ONCE for both gradients (bwd_planes.hip); with 32 output channels the same
-    // partial sums as the two launches
-    const int rows = odin_bwd_planes_rows(d->B, d->H, d->W, d->Cin);
-    if (colsum_rows_out) *colsum_rows_out = rows;
-    if (wslab_rows_out) *wslab_rows_out = rows;
-    if (dry) return 0;
-    return odin_bwd_planes_launch(x, dy, w, aux, dx, colsum_slab, wslab, d->B, d->H, d->W, d->Cin, d->Cout, d->dy_amax,
-                                  d->x_amax, d->dx_amax, stream);
-  }
-  // any other image size: the block-window form of the same launch (blk_planes.hip), 32 output channels
-  if (((dx != nullptr && wslab != nullptr) || dry) && d->KH == 4 && d->KW == 4 && d->stride == 2 && d->pad_t == 1 &&
-      d->pad_l == 1 && d->OH == 2 * d->H && d->OW == 2 * d->W && !d->center &&
-      odin_bwd_blk_applicable(d->B, d->H, d->W, d->Cin, d->Cout)) {
-    const int rows = odin_bwd_blk_rows(d->B, d->H, d->W, d->Cin);
-    if (colsum_rows_out) *colsum_rows_out = rows;
-    if (wslab_rows_out) *wslab_rows_out = rows;
-    if (dry) return 0;
-    return odin_bwd_blk_launch(x, dy, w, aux, aux_act, dx, colsum_slab, wslab, d->B, d->H, d->W, d->Cin, d->Cout,
-                               d->dy_amax, d->x_amax, d->dx_amax, stream);
-  }
-  odin_igemm_pair_begin();
-  int rc = odin_deconv2d_wgrad(x, dy, wslab, wslab_rows_out, d, stream);
-  if (rc == 0) rc = odin_deconv2d_dgrad(dy, w, aux, aux_act, dx, colsum_slab, colsum_rows_out, d, stream);
-  const int rc2 = odin_igemm_pair_end();
-  return rc != 0 ? rc : rc2;
-}
-
-// want_wgrad / want_dgrad: either half may be left out (FactorVAE's TC term back-propagates through the discriminator
-// without touching its weights).  dy_amax / dx_amax: the range words of dy (read) and dx (written when
-// odin_dense_dgrad_keeps_range says so), both optional.
-extern "C" int odin_dense_bwd(const float* x, const float* dy, const float* w, const float* aux, int aux_act,
-                              float* dx, float* colsum_slab, int* colsum_rows_out, float* wslab,
-                              int* wslab_rows_out, int B, int K, int N, int want_wgrad, int want_dgrad,
-                              const uint32_t* dy_amax, uint32_t* dx_amax, void* stream) {
-  return odin_dense_bwd_ranged(x, dy, w, aux, aux_act, dx, colsum_slab, colsum_rows_out, wslab, wslab_rows_out, B, K, N,
-                               want_wgrad, want_dgrad, dy_amax, dx_amax, nullptr, stream);
-}
-
-// + x_amax: the range word of the activation x (the weight gradient's other operand on the two-plane GEMM)
-extern "C" int odin_dense_bwd_ranged(const float* x, const float* dy, const float* w, const float* aux, int aux_act,
-                                     float* dx, float* colsum_slab, int* colsum_rows_out, float* wslab,
-                                     int* wslab_rows_out, int B, int K, int N, int want_wgrad, int want_dgrad,
-                                     const uint32_t* dy_amax, uint32_t* dx_amax, const uint32_t* x_amax,
-                                     void* stream) {
-  if (odin_dense_h_ok(B, K, N) && colsum_slab == nullptr) {
-    int rc = 0;
-    // (a dy without a word is bounded ONCE for both halves)
-    if (dy_amax == nullptr && ((want_wgrad && wslab != nullptr) || (want_dgrad && dx != nullptr))) {
-      dy_amax = odin_range_word_of(dy, (size_t)B * N, nullptr, stream);
-      if (dy_amax == nullptr) return odin_fail(-3, "dense_bwd: no range word for dy");
-    }
-    if (want_wgrad && want_dgrad && wslab != nullptr && dx != nullptr) {
-      // both halves: ONE launch (dense_h.hip: dense_h_pair_kernel), bit-identical to the two
-      if (wslab_rows_out) *wslab_rows_out = 1;
-      if (colsum_rows_out) *colsum_rows_out = 0;
-      return odin_dense_h_bwd_pair(x, dy, w, aux, aux_act, dx, wslab, B, K, N, dy_amax, dx_amax, x_amax, stream);
-    }
-    if (want_wgrad) {
-      if (wslab_rows_out) *wslab_rows_out = 1;
-      if (wslab != nullptr) rc = odin_dense_h_wgrad(x, dy, wslab, B, K, N, dy_amax, x_amax, stream);
-    }
-    if (rc == 0 && want_dgrad) {
-      if (colsum_rows_out) *colsum_rows_out = 0;
-      if (dx != nullptr) rc = odin_dense_h_dgrad(dy, w, aux, aux_act, dx, B, K, N, dy_amax, dx_amax, stream);
-    }
-    return rc;
-  }
-  odin_igemm_pair_begin();
-  int rc = 0;
-  if (want_wgrad) rc = odin_dense_wgrad(x, dy, wslab, wslab_rows_out, B, K, N, stream);
-  if (rc == 0 && want_dgrad)
-    rc = odin_dense_dgrad_ranged(dy, w, aux, aux_act, dx, colsum_slab, colsum_rows_out, B, K, N, dy_amax, dx_amax,
-                                 stream);
-  const int rc2 = odin_igemm_pair_end();
-  return rc != 0 ? rc : rc2;
-}
-
-// 1: the data gradient of this Dense layer (without a column-sum slab) folds max|dx| into dx_amax itself
-extern "C" int odin_dense_dgrad_keeps_range(int B, int K, int N) { return odin_dense_dgrad_tracks(B, K, N) ? 1 : 0; }
 
 // workgroups of job jb that write results (the kernel's three paths), for a launch gx wide
 static int reduce_active_blocks(const odin_reduce_job& jb, int gx) {

@@ -619,12 +619,12 @@ int odin_wgrad_planes_flush(void* stream) {
 }
 
 // fine tensor U [B, H, W, CI], coarse tensor V [B, OH, OW, CO] (the argument order of wgrad.hip's WParams)
-bool odin_wgrad_planes_applicable(int B, int H, int W, int CI, int OH, int OW, int CO, int KH, int KW,
-                                  int S, int pt, int pl, int center) {
+bool odin_wgrad_planes_applicable(const odin_geom& g) {
+  const int B = g.B, H = g.H, W = g.W, CI = g.CI, OH = g.OH, OW = g.OW, CO = g.CO, KH = g.KH, KW = g.KW, S = g.S;
   if (odin_blk_first()) return false;   // (diagnostics: odin_debug_blk_first)
   // (read per call: the A/B tests switch paths inside one process; a captured graph never comes here)
   if (odin_exact_fp32() || ODIN_DIAG_ENV("ODIN_NOPLANES") || ODIN_DIAG_ENV("ODIN_SPLIT") || ODIN_DIAG_ENV("ODIN_NOWPLANES")) return false;
-  return KH == 4 && KW == 4 && S == 2 && pt == 1 && pl == 1 && !center && (CI % 32) == 0 && (CO % 32) == 0 &&
+  return KH == 4 && KW == 4 && S == 2 && g.pt == 1 && g.pl == 1 && !g.center && (CI % 32) == 0 && (CO % 32) == 0 &&
          H == 2 * OH && W == 2 * OW && (OW == 8 || OW == 16 || OW == 32) && (OH % (32 / OW)) == 0 &&
          (size_t)B * H * W * CI * 4 < 0x7FFF0000ull && (size_t)B * OH * OW * CO * 4 < 0x7FFF0000ull &&
          wp_tiles_per_wg(OW, B * (OH / (32 / OW)), (CI / 32) * (CO / 32)) > 0;
