@@ -132,6 +132,19 @@ int odin_conv2d_bwd(const float* x, const float* dy, const float* w, const float
 int odin_deconv2d_bwd(const float* x, const float* dy, const float* w, const float* aux, int aux_act, float* dx,
                       float* colsum_slab, int* colsum_rows_out, float* wslab, int* wslab_rows_out,
                       const odin_conv_desc* d, void* stream);
+/* The FIRST layer's weight gradient folded into the data gradient of the layer above it: d = the second layer, a
+ * Conv2D(32 -> 32, k4, s2) with 16 x 16 outputs, dy / w / aux / aux_act / dx as in odin_conv2d_dgrad (aux_act = ELU;
+ * colsum_slab / colsum_rows_out optional, as there); d0 =
+ * the first layer, a Conv2D(1 -> 32, k4, s2, SAME) on a 64 x 64 image x0 (d0->center honoured).  ONE launch computes dx,
+ * and from the dx tile it holds the partial (dW0 | db0) rows wslab0[g][16 * 32 | 32], g < *wslab0_rows_out, in the
+ * layout of odin_conv2d_wgrad(x0, dx, ..., d0) -- the same fp32 products, summed in that kernel's order inside a
+ * workgroup (the same bits after odin_slab_reduce where both give a workgroup one image: 256 samples on 256 CUs).  dx == NULL: the
+ * gradient is not stored at all (nothing below the first layer needs it); dx != NULL: dx and d->dx_amax exactly as
+ * odin_conv2d_dgrad leaves them.  wslab0 == NULL: dry run (rows only).  -2: shapes outside the kernel, nothing is
+ * launched -- the caller keeps the two calls. */
+int odin_conv2d_dgrad_first(const float* dy, const float* w, const float* aux, int aux_act, float* dx,
+                            float* colsum_slab, int* colsum_rows_out, const odin_conv_desc* d, const float* x0,
+                            float* wslab0, int* wslab0_rows_out, const odin_conv_desc* d0, void* stream);
 /* Dense: either half may be left out (want_wgrad / want_dgrad); dy_amax / dx_amax are the optional range words of dy
  * (read) and dx (written: from the epilogue when odin_dense_dgrad_keeps_range(B, K, N) = 1, by one extra pass
  * otherwise) -- layers with both widths >= 256 run on the

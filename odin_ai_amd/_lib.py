@@ -67,6 +67,7 @@ SIGNATURES = {
     'odin_bernoulli_tail_keeps_range': [I, DP, I],
     'odin_conv2d_bwd': [P, P, P, P, I, P, P, IP, P, IP, DP, P],
     'odin_deconv2d_bwd': [P, P, P, P, I, P, P, IP, P, IP, DP, P],
+    'odin_conv2d_dgrad_first': [P, P, P, I, P, P, IP, DP, P, P, IP, DP, P],
     'odin_dense_bwd': [P, P, P, P, I, P, P, IP, P, IP, I, I, I, I, I, P, P, P],
     'odin_dense_bwd_ranged': [P, P, P, P, I, P, P, IP, P, IP, I, I, I, I, I, P, P, P, P],
     'odin_dense_dgrad_keeps_range': [I, I, I],

@@ -15,6 +15,8 @@ enum Family {
   FCONV_PLANES, FCONV_RING, FCONV_BLK, CONV5_BLK, TCONV_PLANES, TCONV_RING, TCONV_BLK, IGEMM_H, IGEMM,
   WGRAD_PLANES, WGRAD5_BLK, WGRAD_BLK, IGEMM_H_WGRAD, IGEMM_WGRAD,
   BWD_PLANES, BWD_BLK,   // weight + data gradient of a Conv2DTranspose in one launch
+  TCONV_PLANES_FIRST,    // data gradient of the second layer + weight gradient of the first in one launch
+  NOT_SERVED,            // an entry point without a generic form declines the geometry
   BWD_PAIR,              // the two gradient calls inside an odin_igemm_pair_begin / _end bracket
   TINY_DENSE, THIN_DENSE, DENSE_H, DENSE_GEMM
 };
@@ -31,7 +33,7 @@ int traits(Family f) {
     case FCONV_PLANES: case FCONV_BLK: case CONV5_BLK: case TCONV_PLANES: case TCONV_BLK: case IGEMM_H: case DENSE_H:
       return FOLDS_Y | FOLDS_DX | READS_X;
     case WGRAD_PLANES: case WGRAD5_BLK: case WGRAD_BLK: case IGEMM_H_WGRAD: return READS_X;
-    case BWD_PLANES: case BWD_BLK: case DENSE_GEMM: return FOLDS_DX;
+    case BWD_PLANES: case BWD_BLK: case DENSE_GEMM: case TCONV_PLANES_FIRST: return FOLDS_DX;
     default: return 0;   // generic gather, 1x1 stream kernel, the fp32 ring kernels, tiny Dense
   }
 }
@@ -84,6 +86,13 @@ Family select_conv2d_dgrad(const odin_geom& l, const odin_geom& g, int aux_act, 
   if (odin_igemm_h_applicable(1, g)) return IGEMM_H;
   if (igemm_dgrad(1, g, slab, dry)) return IGEMM;
   return GENERIC;
+}
+
+// the same data gradient, taking the weight gradient of the layer below (l0: its forward gather, the FIRST layer of the
+// stack) with it: one family, and no generic form -- the caller keeps the two calls
+Family select_conv2d_dgrad_first(const odin_geom& l, const odin_geom& g, const odin_geom& l0, int aux_act, bool aux_ok) {
+  if (select_conv2d_dgrad(l, g, aux_act, aux_ok, false, false) != TCONV_PLANES) return NOT_SERVED;
+  return odin_tconv_planes_first_applicable(g, l0) ? TCONV_PLANES_FIRST : NOT_SERVED;
 }
 
 Family select_deconv2d_fwd(const odin_geom& g, bool bias, int act) {
@@ -360,6 +369,26 @@ extern "C" int odin_conv2d_bwd(const float* x, const float* dy, const float* w, 
   int rc = odin_conv2d_wgrad(x, dy, wslab, wslab_rows_out, d, stream);
   if (rc == 0) rc = odin_conv2d_dgrad(dy, w, aux, aux_act, dx, colsum_slab, colsum_rows_out, d, stream);
   return pair_end(rc);
+}
+
+// The data gradient of layer d (the SECOND layer) and the weight gradient of the layer below it (d0, the FIRST layer
+// of the stack, input x0) in one launch: dx never has to reach memory (dx == NULL: not stored); colsum_slab (optional) as
+// in odin_conv2d_dgrad, one row per slab row.  wslab0 == NULL: dry run.
+extern "C" int odin_conv2d_dgrad_first(const float* dy, const float* w, const float* aux, int aux_act, float* dx,
+                                       float* colsum_slab, int* colsum_rows_out, const odin_conv_desc* d, const float* x0,
+                                       float* wslab0, int* wslab0_rows_out, const odin_conv_desc* d0, void* stream) {
+  const bool dry = wslab0 == nullptr;
+  const Family f = select_conv2d_dgrad_first(odin_geom_fwd(d), odin_geom_dgrad(d), odin_geom_fwd(d0), aux_act,
+                                             aux != nullptr || dry);
+  if (f != TCONV_PLANES_FIRST) return odin_fail(-2, "conv2d_dgrad_first: shapes outside the kernel");
+  if (!dry && (dy == nullptr || w == nullptr || x0 == nullptr))
+    return odin_fail(-2, "conv2d_dgrad_first: null argument");
+  int rows = 0;
+  const int rc = odin_tconv_planes_first_launch(dy, w, aux, dx, colsum_slab, x0, d0->center, wslab0, &rows, d->B, d->dy_amax,
+                                                d->dx_amax, stream);
+  if (rc == 0 && wslab0_rows_out) *wslab0_rows_out = rows;
+  if (rc == 0 && colsum_rows_out) *colsum_rows_out = rows;
+  return keep_range(rc, f, FOLDS_DX, dx, (size_t)d->B * d->H * d->W * d->Cin, d->dx_amax, stream);
 }
 
 // 1: the data gradient of this layer (as dispatched for `aux_act`, with the aux tensor present and NO column-sum slab)

@@ -173,6 +173,12 @@ int odin_tconv_planes_launch(const float* in, const float* w, const float* bias,
                              const float* target, float* logits, float* llk_part, int* n_part_out,
                              float* slab, const float* scale, int C1, int B, int H, int W, int CI,
                              int CO, int epi, const uint32_t* in_amax, uint32_t* out_amax, void* stream);
+// the data gradient of the SECOND layer of the image stacks, which also forms the FIRST layer's weight gradient from the
+// dx tile it holds (g: the upper layer's data-gradient gather, l0: the first layer's forward gather); out may be null
+bool odin_tconv_planes_first_applicable(const odin_geom& g, const odin_geom& l0);
+int odin_tconv_planes_first_launch(const float* in, const float* w, const float* aux, float* out, float* colsum, const float* img,
+                                   int center0, float* wslab0, int* rows_out, int B, const uint32_t* in_amax,
+                                   uint32_t* out_amax, void* stream);
 
 // weight gradients of the 4x4 / stride-2 layers with both operands as bf16 planes, transposing LDS reads
 // (wgrad_planes.hip)

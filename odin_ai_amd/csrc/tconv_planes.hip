@@ -59,6 +59,11 @@ struct TPParams {
   unsigned* out_amax;       // EPI 2 / 3: range word of `out`, a gradient tensor (may be null)
   long long* stamps;   // diagnostics: s_memtime stamps of workgroup 0 (wave 0: [0,32), wave 4: [32,64))
   int part_off;        // PL instances: byte offset (dynamic LDS) of the partial-sum buffer [tile][q][thread] x 16 bytes
+  // FW instance (the first layer's weight gradient formed from the dx tile, see tp_body)
+  const float* img;    // [B, 64, 64, 1]: the input image of the layer below
+  float* wslab0;       // [gridDim.x][16 * 32 | 32]: one (dW0 | db0) row per workgroup
+  int center0;         // the layer below loads its input as 2 x - 1
+  int fw_off;          // byte offset (dynamic LDS) of the dx stage (256 pixels x 32 ch, tp_fw_addr) + the image patch
 };
 
 #if defined(ODIN_SIM) || !defined(ODIN_DIAG)  // in-kernel stamps: diagnostics build only (make diag)
@@ -114,6 +119,17 @@ struct alignas(8) TpEnt {
   int x, y;
 };
 
+// FW: the dx tile crosses LDS once: [256 pixels of the tile][32 channels] fp32 in 256-byte rows of two pixels, the
+// 16-byte channel groups XOR-swizzled by the row (the 64 lanes of a ds_read_b32 -- 2 pixels x 32 channels -- cover all
+// banks; a 16-lane group of the ds_write_b128 meets each bank twice)
+__host__ __device__ constexpr int tp_fw_addr(int lp, int n) {
+  return (lp >> 1) * 256 + (((((lp & 1) << 3) + (n >> 2)) ^ ((lp >> 1) & 7)) << 4) + (n & 3) * 4;
+}
+constexpr int TP_FW_IMG_STRIDE = 72;                     // floats per staged image row: 4 guard | 64 pixels | 4 guard
+constexpr int TP_FW_IMG_FLOATS = 18 * TP_FW_IMG_STRIDE;  // the 18 image rows under the 8 dx rows of a tile
+constexpr int TP_FW_BYTES = 8 * 4096 + TP_FW_IMG_FLOATS * 4;   // stage + patch (the 16 chains' partials overlay them)
+static_assert(16 * 17 * 32 * 4 <= TP_FW_BYTES, "the partials of the 16 chains overlay the stage and the patch");
+
 struct TpItem {
   float4 v;
   int dst;  // byte offset of the hi-plane store inside the ring
@@ -133,8 +149,19 @@ struct TpItem {
 // PL (round 6): the raw partial sums of the first of two reduction passes stay in LDS ([tile][q][thread] x 16 bytes, the
 // SAME thread reads them back in the second pass) instead of travelling through `out`: decoder3's forward moved 120 MB
 // for 50 MB of algorithmic traffic that way (PMC, profiles/r05_pmc_traffic.json).
-template <int EPI, int C1, int W, int DBG = 0, bool ACC = false, int SCM = 0, bool PL = false>
+// FW (EPI 2, W 16: the data gradient of a Conv2D(32 -> 32, k4, s2) whose input is the output of the FIRST layer,
+// Conv2D(1 -> 32, k4, s2) on a 64 x 64 image): the workgroup also forms the first layer's weight gradient
+//   dW0[kh, kw, 0, c] = sum_(b, oh, ow) dx[b, oh, ow, c] img[b, 2 oh - 1 + kh, 2 ow - 1 + kw]
+// and bias gradient from the finished dx tile, so that dx need not reach memory at all (p.out == nullptr: no store).
+// The pixel is the reduction index and the accumulators hold pixels on lanes: store_q also writes the four channel
+// groups of a lane into a 32 KB stage, the 18 image rows under the tile ride in one float4 per thread (loaded a tile
+// ahead, beside aux) into an LDS patch, and behind the tile's barrier wave v runs dx row v of the tile
+// through 16 v_mfma_f32_32x32x2_f32 (see fw_chain below for the order), followed by a second barrier that frees the
+// stage and the patch for the next epilogue.  fp32 products: dx has no range word before the launch ends, and the kernel this
+// replaces is IEEE fp32.
+template <int EPI, int C1, int W, int DBG = 0, bool ACC = false, int SCM = 0, bool PL = false, bool FW = false>
 __device__ __forceinline__ void tp_body(const TPParams& p) {
+  static_assert(!FW || (EPI == 2 && W == 16 && C1 == 1 && !ACC && !PL), "FW: the 32-channel data gradient, 16-pixel rows");
   constexpr int NPL = TP_NPL;
   constexpr int RP = 64 / W;              // input rows per tile
   constexpr int NSLOT = 2 * RP + 3;       // live rows of a tile (RP + 2) + the next tile's (RP + 1 at an image seam)
@@ -219,6 +246,12 @@ __device__ __forceinline__ void tp_body(const TPParams& p) {
     const int pl = rem >> 3, side = (rem >> 2) & 1, piece = rem & 3;
     *reinterpret_cast<float4*>(ring + sl * RB + pl * PB + (side ? (W + 1) * 64 : 0) + piece * 16) =
         make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+
+  // (FW) the image patch: guard columns and the rows beyond the image stay zero
+  float* fw_img = reinterpret_cast<float*>(smem + p.fw_off + 8 * 4096);
+  if (FW) {
+    for (int e = tid; e < TP_FW_IMG_FLOATS; e += 512) fw_img[e] = 0.f;
   }
 
   // ---- row fills: wave-uniform walk over the padded rows; a wave moves up to two 1 KB items ----
@@ -420,6 +453,49 @@ __device__ __forceinline__ void tp_body(const TPParams& p) {
   // (the bias sits in the main accumulator from the tile's first MFMA on -- biasv below -- so the epilogue adds none:
   // 16 VALU instructions less per tile and wave)
   auto elu_r = [&](int r) { elu_b(r, 0.f); };
+  // ---- (FW) the first layer's weight gradient ----
+  const OdinRun IMG = odin_run(FW ? p.img : nullptr, FW ? (unsigned)((size_t)p.B * 64 * 64 * 4) : 0u);
+  const int fw_rowl = tid >> 4, fw_c4 = tid & 15;   // patch item of this thread: row 16 t - 1 + fw_rowl, 4 pixels (tid < 288)
+  float4 imgP = make_float4(0.f, 0.f, 0.f, 0.f);
+  bool imgokP = false;
+  auto fw_load = [&](int b, int t, float4& v, bool& ok) {
+    const int row = 16 * t - 1 + fw_rowl;
+    ok = tid < 288 && row >= 0 && row < 64;
+    v = odin_run_load4(IMG, ok ? (unsigned)((((b * 64 + row) * 64) + 4 * fw_c4) * 4) : ODIN_OOB);
+  };
+  // Summation order: that of the stand-alone weight gradient it replaces (smallc_wgrad_lds_kernel<1, 1>), so that the
+  // step computes the same bits where the partitions coincide (a workgroup = one image, the benchmark's batch on 256
+  // CUs): v_mfma_f32_32x32x2_f32 with M = 16 taps + the bias row (a = 1), N = 32 channels, K = 2 pixels, ONE chain per
+  // dx row in pixel order; wave v takes row 8 t + v of image tile t into accumulator set t & 1 (that kernel's wave
+  // v + 8 (t & 1) chains rows w and w + 16 of an image), and the 16 chains are combined as it combines its 16 waves.
+  // A[row = lane & 31][k = lane >> 5], B[k][n = lane & 31]: pixel 2 u + k of the row in MFMA u
+  const int fw_k = lane >> 5, fw_j = lane & 31;
+  const bool fw_tap = fw_j < 16;
+  const float fw_aconst = fw_j == 16 ? 1.f : 0.f;
+  // tap (kh, kw) of dx pixel (row, col) reads patch row 2 row + kh, patch column 2 col - 1 + kw + 4
+  const int fw_a_lane = fw_tap ? (2 * wave + (fw_j >> 2)) * TP_FW_IMG_STRIDE + 2 * fw_k + (fw_j & 3) + 3 : 0;
+  f32x16 faccA = f32x16_zero(), faccB = f32x16_zero();
+  auto fw_chain = [&](f32x16 acc) __attribute__((always_inline)) {
+    const float* ib = fw_img + fw_a_lane;
+    const char* sb = smem + p.fw_off;
+#pragma unroll
+    for (int u0 = 0; u0 < 16; u0 += 4) {
+      float av[4], bv[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const float a = ib[4 * (u0 + u)];
+        av[u] = fw_tap ? a : fw_aconst;
+        bv[u] = *reinterpret_cast<const float*>(sb + tp_fw_addr(wave * 32 + 2 * (u0 + u) + fw_k, fw_j));
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) acc = mfma32(av[u], bv[u], acc);
+    }
+    return acc;
+  };
+  // t: the consumed tile's index inside its image
+  auto fw_phase = [&](int t) __attribute__((always_inline)) {
+    if (t & 1) faccB = fw_chain(faccB); else faccA = fw_chain(faccA);
+  };
   char* plds = smem + p.part_off + tid * 16;   // (PL) this thread's 16-byte slot of a (tile, q) block of 512
   int tileP_loc = 0;                            // (PL) the previous tile's index inside this workgroup
   auto store_q = [&](int q) __attribute__((always_inline)) {
@@ -429,6 +505,16 @@ __device__ __forceinline__ void tp_body(const TPParams& p) {
       *reinterpret_cast<float4*>(plds + (tileP_loc * 4 + q) * 8192) =
           make_float4(pa[4 * q], pa[4 * q + 1], pa[4 * q + 2], pa[4 * q + 3]);
       return;
+    }
+    if (FW) {
+      *reinterpret_cast<float4*>(smem + p.fw_off + tp_fw_addr((int)pix_lane, 8 * q + 4 * half)) =
+          make_float4(pa[4 * q], pa[4 * q + 1], pa[4 * q + 2], pa[4 * q + 3]);
+      if (q == 0 && tid < 288) {   // the image rows under the tile, centred where they are real
+        float4 v = imgP;
+        if (p.center0 && imgokP) { v.x = 2.f * v.x - 1.f; v.y = 2.f * v.y - 1.f; v.z = 2.f * v.z - 1.f; v.w = 2.f * v.w - 1.f; }
+        *reinterpret_cast<float4*>(fw_img + fw_rowl * TP_FW_IMG_STRIDE + 4 + 4 * fw_c4) = v;
+      }
+      if (p.out == nullptr) return;   // (wave-uniform) the tile lives and dies in LDS
     }
     odin_run_store4s(OUT, out_lane + 32 * q, tileP_out,
                      make_float4(pa[4 * q], pa[4 * q + 1], pa[4 * q + 2], pa[4 * q + 3]));
@@ -645,6 +731,8 @@ __device__ __forceinline__ void tp_body(const TPParams& p) {
     const unsigned tile_out = tile_pix * (unsigned)p.CO * 4u, tile_tgt = tile_pix * (unsigned)C1 * 4u;
     float4 axN[4], pvN[4];
     float tgtN[(EPI == 3) ? C1 : 1] = {};
+    float4 imgN = make_float4(0.f, 0.f, 0.f, 0.f);
+    bool imgokN = false;
 #pragma unroll
     for (int q = 0; q < 4; ++q) axN[q] = pvN[q] = make_float4(0.f, 0.f, 0.f, 0.f);
     ODIN_SCHED_FENCE();
@@ -665,6 +753,7 @@ __device__ __forceinline__ void tp_body(const TPParams& p) {
 #pragma unroll
           for (int q = 0; q < 4; ++q)
             axN[q] = odin_run_load4s(AUX, out_lane + 32 * q, tile_out);
+          if (FW) fw_load(b_cur, t_cur, imgN, imgokN);
         }
         if (EPI == 3) {
 #pragma unroll
@@ -720,6 +809,7 @@ __device__ __forceinline__ void tp_body(const TPParams& p) {
     tileP_loc = T - T0;
 #pragma unroll
     for (int q = 0; q < 4; ++q) { axP[q] = axN[q]; pvP[q] = pvN[q]; }
+    if (FW) { imgP = imgN; imgokP = imgokN; }
 #pragma unroll
     for (int oc = 0; oc < ((EPI == 3) ? C1 : 1); ++oc) tgtP[oc] = tgtN[oc];
     itA[0] = itB[0];
@@ -736,12 +826,18 @@ __device__ __forceinline__ void tp_body(const TPParams& p) {
 #pragma unroll 1
     for (int T = T0 + 1; T < T1; ++T) {
       sl0 += RP;
+      const int t_cons = t_cur;   // (FW) tile T - 1 inside its image
+      (void)t_cons;
       if (++t_cur == p.tiles_per_img) { t_cur = 0; ++b_cur; ++sl0; }
       if (sl0 >= NSLOT) sl0 -= NSLOT;
       run_tile(TpYes{}, group_b, T);
       TP_STAMP(11);
       __syncthreads();  // every wave is past tile T's rows; tile T + 1's rows are stored
       TP_STAMP(10);
+      if (FW) {   // tile T - 1: the barrier published its dx stage and its image patch
+        fw_phase(t_cons);
+        __syncthreads();   // (tile T's epilogue, inside the next tile's stream, overwrites the stage)
+      }
       if (EPI == 3 && tid == 0) {
         // tile T - 1 closed a sample: its slot carries the sample's (this workgroup's share of the) sum,
         // the other tiles' slots a zero
@@ -760,6 +856,30 @@ __device__ __forceinline__ void tp_body(const TPParams& p) {
     for (int k = 0; k < N_EPI_OPS; ++k) epi_op(k);
   }
   flush_llk(T1 - 1);
+  if (FW) {
+    __syncthreads();   // the last tile's image patch
+    fw_phase(t_cur);
+    __syncthreads();   // every wave is done with the stage and the patch: the 16 chains overlay them
+    // chain c = wave + 8 * set: rows 0 .. 16 (taps, bias) x 32 channels; accumulator register r of lane (k, n) holds row
+    // (r & 3) + 8 (r >> 2) + 4 k
+    float* part = reinterpret_cast<float*>(smem + p.fw_off);
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int row = (r & 3) + 8 * (r >> 2) + 4 * fw_k;
+      if (row <= 16) {
+        part[(wave * 17 + row) * 32 + fw_j] = faccA[r];
+        part[((wave + 8) * 17 + row) * 32 + fw_j] = faccB[r];
+      }
+    }
+    __syncthreads();
+    for (int e = tid; e < 17 * 32; e += 512) {
+      float tt = 0.f;
+#pragma unroll
+      for (int c = 0; c < 16; c += 4)
+        tt += (part[c * 544 + e] + part[(c + 1) * 544 + e]) + (part[(c + 2) * 544 + e] + part[(c + 3) * 544 + e]);
+      p.wslab0[(size_t)blockIdx.x * (17 * 32) + e] = tt;
+    }
+  }
 
 #if defined(ODIN_DIAG) && !defined(ODIN_SIM)
   if (p.stamps != nullptr && blockIdx.x == 0 && blockIdx.y == 0 && tid == 0) {
@@ -832,9 +952,9 @@ __device__ __forceinline__ void tp_body(const TPParams& p) {
   }
 }
 
-template <int EPI, int C1, int W, int DBG = 0, bool ACC = false, int SCM = 0>
+template <int EPI, int C1, int W, int DBG = 0, bool ACC = false, int SCM = 0, bool FW = false>
 __global__ __launch_bounds__(512) void tconv_planes_kernel(TPParams p) {
-  tp_body<EPI, C1, W, DBG, ACC, SCM>(p);
+  tp_body<EPI, C1, W, DBG, ACC, SCM, false, FW>(p);
 }
 
 // 64 reduction channels in ONE launch: both 32-channel passes inside the kernel (round 3 launched them separately: a
@@ -868,12 +988,12 @@ constexpr int TP_LDS_MAX = 152 * 1024;   // (dynamic; + up to 2 x 4.3 KB static 
 int tp_ring_bytes(int W) { return TP_WBYTES + (2 * (64 / W) + 3) * TP_NPL * (W + 2) * 64; }
 int tp_fill_bytes(int W) { return 8 * 2 * (W == 32 ? 2 : W == 16 ? 4 : 8); }
 // tiles per workgroup: the chip filled once when the table fits, more workgroups otherwise; -1: does not fit
-int tp_tiles_per_wg(int W, int n_tiles, int gy) {
+int tp_tiles_per_wg(int W, int n_tiles, int gy, int extra_lds = 0) {
   int cap = odin_num_cus() / gy;
   if (cap < 1) cap = 1;
   if (cap > ODIN_MAX_COLSUM_BLOCKS) cap = ODIN_MAX_COLSUM_BLOCKS;
   int tpw = (n_tiles + cap - 1) / cap;
-  const int limit = (TP_LDS_MAX - tp_ring_bytes(W)) / tp_fill_bytes(W) - 3;
+  const int limit = (TP_LDS_MAX - extra_lds - tp_ring_bytes(W)) / tp_fill_bytes(W) - 3;
   if (tpw > limit) tpw = limit;
   if ((n_tiles + tpw - 1) / tpw > ODIN_MAX_COLSUM_BLOCKS) return -1;
   return tpw;
@@ -921,6 +1041,28 @@ int tp_launch_w(const TPParams& p, int W, dim3 grid, void* stream) {
   else if (W == 16) ODIN_LAUNCH((tconv_planes_kernel<EPI, C1, 16, 0, ACC, SC>), grid, dim3(512), lds, stream, p);
   else ODIN_LAUNCH((tconv_planes_kernel<EPI, C1, W3, 0, ACC, SC>), grid, dim3(512), lds, stream, p);
   return odin_check_launch("tconv_planes(f16x2)");
+}
+
+// the data gradient that also forms the first layer's weight gradient (FW): the dx stage and the image patch behind
+// the fill table
+int tp_launch_fw(const TPParams& p0, dim3 grid, void* stream) {
+  TPParams p = p0;
+  size_t lds = (size_t)tp_ring_bytes(16) + (size_t)(p.tiles_per_wg + 3) * tp_fill_bytes(16);
+  lds = (lds + 255) & ~(size_t)255;
+  p.fw_off = (int)lds;
+  lds += TP_FW_BYTES;
+#ifndef ODIN_SIM
+  static bool attr_done = false;
+  if (!attr_done) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&tconv_planes_kernel<2, 1, 16, 0, false, 1, true>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, TP_LDS_MAX) != hipSuccess)
+      (void)hipGetLastError();
+    attr_done = true;
+  }
+#endif
+  if (lds > (size_t)TP_LDS_MAX) return odin_fail(-2, "tconv_planes(first): LDS");
+  ODIN_LAUNCH((tconv_planes_kernel<2, 1, 16, 0, false, 1, true>), grid, dim3(512), lds, stream, p);
+  return odin_check_launch("tconv_planes+wgrad0(f16x2)");
 }
 
 // the two-pass kernels: dynamic LDS up to 160 000 bytes (2 x 1.2 KB of static arrays on top: 160 KiB per CU)
@@ -1046,4 +1188,37 @@ int odin_tconv_planes_launch(const float* in, const float* w, const float* bias,
   if (C1 == 1) return aw ? tp_launch_w<3, 1, false, 2>(p, W, grid, stream) : tp_launch_w<3, 1, false, 0>(p, W, grid, stream);
   if (C1 == 3) return aw ? tp_launch_w<3, 3, false, 2>(p, W, grid, stream) : tp_launch_w<3, 3, false, 0>(p, W, grid, stream);
   return odin_fail(-2, "tconv_planes tail: one or three logit maps only");
+}
+
+// ---- the data gradient of the second layer with the first layer's weight gradient formed from the dx tile (FW) ----
+// g: the upper layer's data-gradient gather (dy1 -> dx), l0: the first layer's forward gather (image -> the tensor dx is
+// the gradient of)
+bool odin_tconv_planes_first_applicable(const odin_geom& g, const odin_geom& l0) {
+  return odin_tconv_planes_applicable(g, 2, 1) && g.H == 16 && g.W == 16 && g.CI == 32 && g.CO == 32 && l0.B == g.B &&
+         l0.H == 64 && l0.W == 64 && l0.CI == 1 && l0.OH == 32 && l0.OW == 32 && l0.CO == 32 && l0.KH == 4 && l0.KW == 4 &&
+         l0.S == 2 && l0.pt == 1 && l0.pl == 1 && (size_t)g.B * 64 * 64 * 4 < (1ull << 31) &&
+         tp_tiles_per_wg(16, g.B * 4, 1, TP_FW_BYTES + 256) > 0;
+}
+
+// out may be null (dx is not stored), colsum too ([rows][32] column sums of dx); wslab0 == nullptr: dry run (rows only).  One slab row [16 * 32 | 32] per workgroup.
+int odin_tconv_planes_first_launch(const float* in, const float* w, const float* aux, float* out, float* colsum, const float* img,
+                                   int center0, float* wslab0, int* rows_out, int B, const uint32_t* in_amax,
+                                   uint32_t* out_amax, void* stream) {
+  TPParams p;
+  memset(&p, 0, sizeof(p));
+  p.in = in; p.w = w; p.aux = aux; p.out = out; p.colsum = colsum; p.img = img; p.wslab0 = wslab0; p.center0 = center0;
+  p.B = B; p.H = 16; p.CO = 32;
+  p.CS = 32; p.ci_off = 0;
+  p.stamps = g_tp_stamps;
+  p.tiles_per_img = 4;
+  p.n_tiles = B * 4;
+  p.tiles_per_wg = tp_tiles_per_wg(16, p.n_tiles, 1, TP_FW_BYTES + 256);
+  if (p.tiles_per_wg <= 0) return odin_fail(-2, "tconv_planes(first): too many tiles for the fill table");
+  const int gx = (p.n_tiles + p.tiles_per_wg - 1) / p.tiles_per_wg;
+  if (rows_out) *rows_out = gx;
+  if (wslab0 == nullptr) return 0;  // dry run
+  p.in_amax = odin_range_word_of(in, (size_t)B * 16 * 16 * 32, in_amax, stream);
+  if (p.in_amax == nullptr) return odin_fail(-3, "tconv_planes(first): no range word for the gradient input");
+  p.out_amax = out != nullptr ? out_amax : nullptr;
+  return tp_launch_fw(p, dim3(gx, 1, 1), stream);
 }

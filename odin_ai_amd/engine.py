@@ -136,8 +136,11 @@ class NetProgram:
   def __init__(self, lib, recs: List[LayerRec], B: int, device, params: torch.Tensor,
                grads: torch.Tensor, max_rows: int, range_words: Optional[torch.Tensor] = None,
                act_words: Optional[torch.Tensor] = None, use_act_words: bool = True, small_wgrad_gf: float = 0.8,
-               direct_wgrad: bool = False):
+               direct_wgrad: bool = False, fuse_first_wgrad: bool = False):
     self.lib, self.recs, self.B, self.device = lib, recs, B, device
+    # the first layer's weight gradient formed inside the data gradient of the layer above it (include/odin_hip.h:
+    # odin_conv2d_dgrad_first): decided from the layer records, so that a network without the pair issues no call for it
+    self.fuse_first = bool(fuse_first_wgrad) and self._first_pair_qualifies()
     self.params, self.grads = params, grads
     f32 = dict(dtype=torch.float32, device=device)
     # one range word per outs[i] too (round 5, include/odin_hip.h: odin_conv_desc.x_amax / y_amax): max |activation|,
@@ -265,6 +268,16 @@ class NetProgram:
           else self.lib.odin_deconv2d_dgrad_keeps_range)
     return bool(fn(C.byref(self.descs[j]), ACT[self.recs[j - 1].act]))
 
+  def _first_pair_qualifies(self) -> bool:
+    """Conv2D(1 -> 32, k4, s2) on a 64 x 64 image under an ELU, then Conv2D(32 -> 32, k4, s2): the one geometry
+    odin_conv2d_dgrad_first serves"""
+    if len(self.recs) < 2 or any(r.kind != 'conv' for r in self.recs[:2]):
+      return False
+    r0, r1 = self.recs[0], self.recs[1]
+    k4s2 = dict(K=4, stride=2, pad_t=1, pad_l=1)
+    return (r0.act == 'elu' and r0.desc == dict(H=64, W=64, Cin=1, OH=32, OW=32, Cout=32, **k4s2) and
+            r1.desc == dict(H=32, W=32, Cin=32, OH=16, OW=16, Cout=32, **k4s2) and not r1.center)
+
   def bslabs_wanted(self, i: int) -> bool:
     """does layer i take its bias gradient from the column sums of its successor's data gradient?"""
     return self.recs[i].kind == 'deconv'
@@ -279,6 +292,15 @@ class NetProgram:
       if r.kind == 'conv':
         lib.odin_conv2d_wgrad(None, None, None, C.byref(rows), C.byref(d), None)
         n = r.w_n + r.b_n
+        if i == 0 and self.fuse_first:
+          # (the fused launch writes one row per workgroup of the data gradient above: the slab holds either form)
+          r1 = C.c_int(0)
+          try:
+            lib.odin_conv2d_dgrad_first(None, None, None, ACT[r.act], None, None, None, C.byref(self.descs[1]), None, None,
+                                        C.byref(r1), C.byref(d), None)
+            rows.value = max(rows.value, r1.value)
+          except _lib.OdinError:   # (the library declines: the plane kernels are switched off)
+            self.fuse_first = False
       elif r.kind == 'deconv':
         lib.odin_deconv2d_wgrad(None, None, None, C.byref(rows), C.byref(d), None)
         # (the one-call backward may write more rows than the weight gradient alone: bwd_planes.hip with 64 output
@@ -337,10 +359,15 @@ class NetProgram:
   def backward(self, x: torch.Tensor, gout_last: torch.Tensor, st,
                dx_out: Optional[torch.Tensor] = None, last: Optional[int] = None,
                skip_bias_of_last: bool = False, data_only: bool = False,
-               fork=None, side_jobs: Optional[list] = None, first: int = 0) -> List[ReduceJob]:
+               fork=None, side_jobs: Optional[list] = None, first: int = 0,
+               fuse_first: bool = False) -> List[ReduceJob]:
     """gout_last: dL/d(pre-activation output of the last layer).  If dx_out is given the
     gradient wrt the network input is written there.  `first` > 0 stops above layer `first`: its data
-    gradient still lands in gouts[first - 1], layers below are the caller's.  Returns the slab-reduce jobs."""
+    gradient still lands in gouts[first - 1], layers below are the caller's.  `fuse_first`: where the program planned
+    it, layer 1's data gradient also forms layer 0's weight gradient and gouts[0] is never written (the caller says
+    whether anything reads gouts[0]).  Returns the slab-reduce jobs."""
+    fuse_first = (fuse_first and self.fuse_first and first == 0 and dx_out is None and not data_only and
+                  (fork is None or not (fork.wants(self.small_wgrad[0]) or fork.wants(self.small_wgrad[1]))))
     lib, B = self.lib, self.B
     n = len(self.recs) if last is None else last + 1
     jobs: List[ReduceJob] = []
@@ -368,6 +395,19 @@ class NetProgram:
       # a launch (include/odin_hip.h: odin_conv2d_bwd)
       both = (not data_only) and dst is not None and wst is st
       wrows = C.c_int(0)
+      if fuse_first and i == 1:
+        # layer 1's weight gradient as ever; its data gradient takes layer 0's weight gradient with it
+        r0, slab0, rows0 = self.recs[0], self.wslabs[0], C.c_int(0)
+        lib.odin_conv2d_wgrad(xin.data_ptr(), g.data_ptr(), slab.data_ptr(), C.byref(wrows), C.byref(d), st)
+        lib.odin_conv2d_dgrad_first(g.data_ptr(), self.w(1).data_ptr(), auxp, aux_act, None, None, None, C.byref(d),
+                                    x.data_ptr(),
+                                    slab0.data_ptr(), C.byref(rows0), C.byref(self.descs[0]), st)
+        assert 0 < wrows.value <= self.wrows[1] and 0 < rows0.value <= self.wrows[0]
+        jobs.append(ReduceJob(slab.data_ptr(), self.grads[r.w_off:].data_ptr(), slab.shape[1], wrows.value,
+                              slab.shape[1], 0))
+        jobs.append(ReduceJob(slab0.data_ptr(), self.grads[r0.w_off:].data_ptr(), slab0.shape[1], rows0.value,
+                              slab0.shape[1], 0))
+        break
       if both:
         if r.kind == 'conv':
           lib.odin_conv2d_bwd(xin.data_ptr(), g.data_ptr(), self.w(i).data_ptr(), auxp, aux_act, dst.data_ptr(),
@@ -474,7 +514,7 @@ class VAEEngine:
                range_words: Optional[torch.Tensor] = None, *,
                act_words: bool = True, hyper_ring: bool = True, hyper_ring_rows: int = 128, fuse_norm: bool = True,
                overlap_wgrad: Optional[str] = None, early_reduce: bool = False, defer_wgrad: bool = False,
-               side_streams: int = 2, small_wgrad_gf: float = 0.8, dp_buckets: Optional[int] = None,
+               fuse_first_wgrad: bool = True, side_streams: int = 2, small_wgrad_gf: float = 0.8, dp_buckets: Optional[int] = None,
                neck: bool = True, neck_bwd: Optional[bool] = None, static_top_word: bool = True,
                latent_reg: Optional[str] = None, reg_coef: float = 1.0, mmd_kernel: str = 'gaussian',
                mmd_prior_samples: int = 100, dip_lambda: Tuple[float, float] = (1.0, 2.0), prior_seed: int = 0,
@@ -494,6 +534,8 @@ class VAEEngine:
                        profiles/r05_ab_same_call.txt; kept for the multi-bucket DP step's tests)
       early_reduce     with overlap_wgrad: the decoder's slabs reduced on a side stream beside the encoder's backward
       defer_wgrad      the plane weight gradients of a step as ONE launch at the end of the backward pass (slower)
+      fuse_first_wgrad the first encoder layer's weight gradient inside the data gradient of the layer above it, which
+                       then stores no gradient (the dSprites-shaped encoders); False: the two launches
       side_streams     side streams the overlaps rotate over
       small_wgrad_gf   GFLOP below which a weight gradient counts as 'small' for overlap_wgrad
       dp_buckets       gradient buckets of the data-parallel step (default: 2 from 4 ranks and 8 MB up, else 1)
@@ -625,7 +667,7 @@ class VAEEngine:
     gw, aw = self.range_words[:nl * RANGE_WORDS], self.range_words[nl * RANGE_WORDS:2 * nl * RANGE_WORDS]
     self.enc = NetProgram(self.lib, self.enc_recs, B, self.device, self.params, self.grads, mr,
                           range_words=gw[:ne * RANGE_WORDS], act_words=aw[:ne * RANGE_WORDS],
-                          use_act_words=act_words, small_wgrad_gf=small_wgrad_gf)
+                          use_act_words=act_words, small_wgrad_gf=small_wgrad_gf, fuse_first_wgrad=fuse_first_wgrad)
     self.dec = NetProgram(self.lib, self.dec_recs, B, self.device, self.params, self.grads, mr,
                           range_words=gw[ne * RANGE_WORDS:], act_words=aw[ne * RANGE_WORDS:],
                           use_act_words=act_words, small_wgrad_gf=small_wgrad_gf)
@@ -1872,7 +1914,8 @@ class VAEEngine:
     elif self._bwd_neck():
       ne = len(self.enc_recs)
       self._neck_bwd(dzx, tl, ts, st, jobs)
-      jobs += self.enc.backward(self.x, self.enc.gouts[ne - 3], st, fork=fork, last=ne - 3)
+      jobs += self.enc.backward(self.x, self.enc.gouts[ne - 3], st, fork=fork, last=ne - 3,
+                                fuse_first=self._fuse_first_now())
     elif self._bwd_block():
       r0 = self.dec_recs[0]
       lib.odin_latent_block_bwd(self.dec.gouts[0].data_ptr(), self.dec.w(0).data_ptr(), self.z.data_ptr(),
@@ -1902,7 +1945,7 @@ class VAEEngine:
       if bslab is not None:
         jobs.append(self._slab_job(bslab, last.b_off, rows.value))
     if not self._bwd_neck():
-      jobs += self.enc.backward(self.x, self.enc.gouts[-1], st, fork=fork)
+      jobs += self.enc.backward(self.x, self.enc.gouts[-1], st, fork=fork, fuse_first=self._fuse_first_now())
     if self.vamp_K is not None:
       self._backward_pseudo(st, jobs, late_jobs)
     jobs += late_jobs
@@ -1912,6 +1955,11 @@ class VAEEngine:
     rw = self.range_words
     jobs.append(ReduceJob(rw.data_ptr(), rw.data_ptr(), rw.numel(), 0, rw.numel(), 0))
     self._act_words_dirty = False
+
+  def _fuse_first_now(self) -> bool:
+    """may this pass leave enc.gouts[0] unwritten?  Not while the plane weight gradients are collected for one launch,
+    and not under the range audit, which reads the tensor"""
+    return not self.defer_wgrad and not self.debug_check_ranges
 
   def _reduce_slabs(self, jobs, early, st):
     """the step's last backward launch: every slab job of the pass (with the gradient norm's stage 1 where it rides)"""
