@@ -222,6 +222,37 @@ int odin_latent_bwd(const float* p, const float* eps, const float* z, const floa
                     const float* dloc_x, const float* dscale_x, float* dp, int B, int D,
                     int analytic, void* stream);
 
+/* ---- latent posterior q(z|x) = MultivariateNormalTriL(loc, L): the full-covariance Gaussian (latent_tril.hip)
+ * MultivariateNormalLayer.new with covariance='tril' (odin/bay/layers/continuous.py:459-474; RVconf(D, 'mvntril',
+ * projection=True), odin/bay/distribution_alias.py:22-23); the prior stays N(0, I) (random_variable.py:80-86).
+ * p [B, D + M], M = D (D + 1) / 2: loc = p[:, :D], r = p[:, D:] (loc_activation None) and
+ *   L = FillScaleTriL(diag_bijector=softplus, diag_shift=1e-5)(r): r[D:] followed by r reversed are D * D values, read
+ *   row-major as a D x D matrix of which the lower triangle is kept -- for j <= i and k = i D + j:
+ *     L_raw[i][j] = r[D + k] if k < M - D, else r[D D - 1 - k]      (r = [1 .. 6] -> [[4, 0, 0], [6, 5, 0], [3, 2, 1]])
+ *   L_ii = softplus(L_raw_ii) + 1e-5, off-diagonal entries unchanged.
+ * z = loc + L eps;  log q(z) = -1/2 |eps|^2 - sum_i log L_ii - D/2 log 2 pi;  log p(z) = -1/2 |z|^2 - D/2 log 2 pi.
+ * KL as odin_latent_fwd's `analytic`: 0 = the single-sample Monte-Carlo log q(z) - log p(z) at the z written
+ * (helpers.py:267-276), 1 = the closed form 1/2 (|L|_F^2 + |loc|^2 - D) - sum_i log L_ii; 2 (KL(p || q): needs the
+ * inverse of L) is refused.  free_bits / capacity / fbmask act on the per-sample scalar exactly as in odin_latent_fwd.
+ * backward, with w = klw[0] fbmask_b and g = dz + dz_extra (either may be NULL):
+ *   analytic 0: gz = g + w z; dloc = gz;  dL_ij = gz_i eps_j - w delta_ij / L_ii
+ *   analytic 1: dloc = g + w loc;         dL_ij = g_i eps_j + w (L_ij - delta_ij / L_ii)
+ *   dr = dL_ij off the diagonal, dL_ii sigmoid(L_raw_ii) on it (through the inverse of the fill map)
+ * Every element of dp [B, D + M] is written exactly once, no float atomics: bit-reproducible.  dp_amax (optional): the
+ * range word of dp, max |dp| folded in (the projection's gradient kernels read it where they run on two planes: both
+ * widths >= 256 and multiples of 8, at least 32 rows -- D = 29, 32, 45, ..., not D = 22 with its 275 columns).  klw is a DEVICE scalar as in odin_latent_bwd.
+ * odin_latent_tril_sample_logprob: the companion of odin_latent_sample_logprob (p: [B, D + M], eps / z: [n, B, D],
+ * logq / logp: [n, B]).
+ * Limits (a negative return code otherwise, nothing launched, no output touched): 1 <= D <= 64 (one row of L per lane of
+ * a wave), 1 <= B (n B) <= 2^31 - 16. */
+int odin_latent_tril_fwd(const float* p, const float* eps, float* z, float* kl, float* fbmask, int B, int D,
+                         int analytic, float free_bits, const float* capacity, void* stream);
+int odin_latent_tril_bwd(const float* p, const float* eps, const float* z, const float* dz, const float* dz_extra,
+                         const float* fbmask, const float* klw, float* dp, uint32_t* dp_amax, int B, int D,
+                         int analytic, void* stream);
+int odin_latent_tril_sample_logprob(const float* p, const float* eps, float* z, float* logq, float* logp, int n,
+                                    int B, int D, void* stream);
+
 /* ---- the bottleneck as one launch per direction (latent_block.hip): DistributionDense(P -> 2D) ->
  * MVNDiag(loc, softplus(raw)) -> reparameterised sample + KL term -> the decoder's first Dense(D -> N0)
  * (dense_distribution.py DistributionDense; variational_autoencoder.py:515-542; helpers.py:236-286;

@@ -98,6 +98,9 @@ SIGNATURES = {
     'odin_slab_reduce': [C.POINTER(ReduceJob), I, P],
     'odin_latent_fwd': [P, P, P, P, P, I, I, I, F, P, P],
     'odin_latent_bwd': [P, P, P, P, P, P, P, P, P, P, I, I, I, P],
+    'odin_latent_tril_fwd': [P, P, P, P, P, I, I, I, F, P, P],
+    'odin_latent_tril_bwd': [P, P, P, P, P, P, P, P, P, I, I, I, P],
+    'odin_latent_tril_sample_logprob': [P, P, P, P, P, I, I, I, P],
     'odin_latent_block_rows': [I, I, I, I],
     'odin_latent_block_fwd': [P, P, P, P, P, C.c_uint64, P, P, P, P, P, P, P, P, I, I, I, I, I, I, F, P, P],
     'odin_latent_block_bwd': [P, P, P, P, P, P, P, P, P, P, P, P, I, P, P, P, P, P, I, I, I, I, I, P, P],

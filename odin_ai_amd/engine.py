@@ -521,7 +521,8 @@ class VAEEngine:
                vamprior_components: Optional[int] = None, pseudoinputs_mean: float = -0.05,
                pseudoinputs_std: float = 0.01, pseudoinputs=None,
                vq_codes: Optional[int] = None, vq_code_size: Optional[int] = None, vq_commitment: float = 0.25,
-               vq_ema: bool = False, vq_ema_decay: float = 0.99, vq_epsilon: float = 1e-5, vq_state=None):
+               vq_ema: bool = False, vq_ema_decay: float = 0.99, vq_epsilon: float = 1e-5, vq_state=None,
+               latent_cov: str = 'diag'):
     """The keyword-only arguments are the engine's launch-order / A-B options (tests and tools pass them; the engine
     reads no environment variable):
       act_words        activation range words for the two-plane consumers; False: unscaled planes
@@ -571,7 +572,13 @@ class VAEEngine:
       vq_ema          False: the codebook [K, Cs] is the LAST entry of the parameter layout (key ('vq', 'codebook')) and
                       the `latents` term trains it; True: it lives outside the layout with ema_counts / ema_means and
                       the step's backward launch moves it (decay vq_ema_decay, vq_epsilon in the denominator)
-      vq_state        (codebook, ema_counts, ema_means) of another engine of the same model (vq_ema=True only)"""
+      vq_state        (codebook, ema_counts, ema_means) of another engine of the same model (vq_ema=True only)
+    The full-covariance Gaussian posterior (latent_tril.hip; excludes tc, latent_reg='dip_*',
+    vamprior_components, vq_codes, reverse=False, data parallelism, shared range_words and an explicit neck_bwd; the
+    neck and the latent block are not planned -- `neck` is ignored; 1 <= zdim <= 64):
+      latent_cov      'diag' | 'tril': q(z|x) = MultivariateNormalTriL(loc, L); the projection is hdim -> D + D (D + 1) / 2
+                      (loc | the raw values FillScaleTriL lays out as L), `p` / `dp` have that width; latent_reg='mmd'
+                      stays available (it reads z only)"""
     self.lib = lib if lib is not None else _lib.load()
     self.device = torch.device(device)
     self.B, self.D = int(batch_size), int(zdim)
@@ -581,6 +588,9 @@ class VAEEngine:
     # KL form handed to the latent kernels: 0 = Monte-Carlo, 1 = closed-form KL(q||p),
     # 2 = closed-form KL(p||q) (`reverse=False`, odin/bay/helpers.py:261-265)
     self.observation = observation
+    if latent_cov not in ('diag', 'tril'):
+      raise ValueError(f"latent_cov={latent_cov!r}: expected 'diag' or 'tril'")
+    self.latent_cov = latent_cov
     self.set_kl_form(analytic, reverse)
     self.free_bits = -1.0 if free_bits is None else float(free_bits)
     self.tc_mode, self.world_size, self.seed = tc, int(world_size), int(seed)
@@ -606,6 +616,10 @@ class VAEEngine:
       self._check_vq(free_bits, tc, latent_reg, capacity, range_words, neck_bwd)
       self.vq_cw, self.vq_ema = float(vq_commitment), bool(vq_ema)
       self.vq_decay, self.vq_eps = float(vq_ema_decay), float(vq_epsilon)
+    if latent_cov == 'tril':
+      self._check_tril(tc, latent_reg, vamprior_components, vq_codes, range_words, neck_bwd)
+    # width of the latent projection: (loc | raw scale) or (loc | the D (D + 1) / 2 raw entries of L)
+    self.pw = self.D + self.D * (self.D + 1) // 2 if latent_cov == 'tril' else 2 * self.D
     f32 = dict(dtype=torch.float32, device=self.device)
     # ---- parameters ----
     self.layout = ParamLayout()
@@ -613,8 +627,8 @@ class VAEEngine:
     assert len(eo) == 1, 'encoder must end with a flat output'
     self.hdim = eo[0]
     if self.vq_K is None:
-      self.lat_w_off = self.layout.add(('lat', 'w'), (self.hdim, 2 * self.D))
-      self.lat_b_off = self.layout.add(('lat', 'b'), (2 * self.D,))
+      self.lat_w_off = self.layout.add(('lat', 'w'), (self.hdim, self.pw))
+      self.lat_b_off = self.layout.add(('lat', 'b'), (self.pw,))
     else:
       # no latent projection (VectorQuantizer has none): the decoder reads z_q [B, H]
       self.lat_w_off = self.lat_b_off = 0
@@ -661,6 +675,8 @@ class VAEEngine:
     npw = 2 * ne if self.vamp_K is not None else 0
     if self.vq_K is not None:
       npw = 1   # (the word of z_q, right behind the activation words)
+    if latent_cov == 'tril':
+      npw = 1   # (the word of dp: the projection's two-plane gradient kernels read it)
     self.range_words = (range_words if range_words is not None else
                         torch.zeros((2 * nl + npw) * RANGE_WORDS, dtype=torch.int32, device=self.device))
     assert self.range_words.numel() == (2 * nl + npw) * RANGE_WORDS
@@ -680,8 +696,8 @@ class VAEEngine:
     self._bern_keeps_top = observation == 'bernoulli' and bool(static_top_word)
     if self._bern_keeps_top:
       self.dec.set_top_word(True)
-    self.p = torch.empty(B, 2 * D, **f32)
-    self.dp = torch.empty(B, 2 * D, **f32)
+    self.p = torch.empty(B, self.pw, **f32)
+    self.dp = torch.empty(B, self.pw, **f32)
     self.eps = torch.zeros(B, D, **f32)
     self.z = torch.empty(B, D, **f32)
     self.dz = torch.empty(B, D, **f32)
@@ -701,8 +717,8 @@ class VAEEngine:
     self.n_part = 0
     if self.vq_K is None:
       rows = C.c_int(0)
-      self.lib.odin_dense_wgrad(None, None, None, C.byref(rows), B, self.hdim, 2 * D, None)
-      self.lat_slab = torch.empty(rows.value, self.hdim * 2 * D + 2 * D, **f32)
+      self.lib.odin_dense_wgrad(None, None, None, C.byref(rows), B, self.hdim, self.pw, None)
+      self.lat_slab = torch.empty(rows.value, self.hdim * self.pw + self.pw, **f32)
       self.lat_rows = rows.value
     if tc == 'betatc':
       self.tc_ws = torch.zeros(self.lib.odin_total_correlation_workspace(
@@ -723,9 +739,12 @@ class VAEEngine:
     if self.vq_K is None:
       self._plan_fused_tail(f32)
       self._plan_gauss_head(f32)
-      self._plan_latent_block(f32)
-      self._neck_bwd_opt = neck_bwd
-      self._plan_neck(f32, bool(neck))
+      if latent_cov == 'tril':
+        self._plan_tril(bool(act_words))
+      else:
+        self._plan_latent_block(f32)
+        self._neck_bwd_opt = neck_bwd
+        self._plan_neck(f32, bool(neck))
     else:
       self._plan_vq(f32, own_params, vq_state)
     if self.vamp_K is not None:
@@ -1054,6 +1073,42 @@ class VAEEngine:
     if neck_bwd is not None:
       raise NotImplementedError('vq_codes with neck_bwd: the fused neck needs the Gaussian latent block')
 
+  # ---- full-covariance posterior (latent_tril.hip) -------------------------------------------------------
+  def _check_tril(self, tc, latent_reg, vamprior_components, vq_codes, range_words, neck_bwd):
+    if not 1 <= self.D <= 64:
+      raise ValueError(f"latent_cov='tril': zdim={self.D} outside the kernel (1 .. 64: a row of L per lane)")
+    if tc is not None:
+      raise ValueError(f"latent_cov='tril' cannot be combined with tc={tc!r} (the estimator reads a diagonal scale)")
+    if latent_reg in ('dip_i', 'dip_ii'):
+      raise ValueError(f"latent_cov='tril' cannot be combined with latent_reg={latent_reg!r} "
+                       f'(the penalty reads a diagonal scale)')
+    if vamprior_components is not None:
+      raise ValueError("latent_cov='tril' cannot be combined with vamprior_components (the mixture's components "
+                       'read a diagonal scale)')
+    if vq_codes is not None:
+      raise ValueError("latent_cov='tril' cannot be combined with vq_codes (there is no Gaussian posterior)")
+    if self.is_dp:
+      raise NotImplementedError("latent_cov='tril' under data parallelism (world_size > 1 / force_dp) is not offered")
+    if range_words is not None:
+      raise NotImplementedError("latent_cov='tril' on shared range_words is not offered")
+    if neck_bwd:
+      raise NotImplementedError("latent_cov='tril' with neck_bwd: the fused neck holds the diagonal latent block")
+
+  def _plan_tril(self, act_words: bool):
+    """the unfused latent slot only (`neck` / the latent block are not planned); the two range words of the projection
+    where its launches read planes (both widths >= 256 and multiples of 8, a batch of at least 32: D = 29, 32, 45, ...,
+    not D = 22 with its 275 columns): the encoder's last layer keeps the word of h_e, the latent backward that of dp"""
+    self.lat_block = self._used_block = False
+    self.neck = self._used_neck = False
+    self._neck_bwd_opt = None
+    ne, nl = len(self.enc_recs), len(self.enc_recs) + len(self.dec_recs)
+    self._tril_dp_word = self.range_words.data_ptr() + 4 * RANGE_WORDS * 2 * nl
+    self._tril_x_word = None
+    if act_words and self.lib.odin_dense_reads_x_range(self.B, self.hdim, self.pw):
+      self._tril_x_word = self.enc.y_word[ne - 1] = self.enc.aword(ne - 1)
+      if self.enc.descs[ne - 1] is not None:
+        self.enc.descs[ne - 1].y_amax = self._tril_x_word
+
   def _resolve_vq_code_size(self, code_size):
     H, K = self.hdim, self.vq_K
     Cs = H if code_size is None else int(code_size)
@@ -1155,6 +1210,8 @@ class VAEEngine:
       # calls tf.convert_to_tensor on the prior (helpers.py:267-276 with q_sample=None)
       raise TypeError('reverse=False needs analytic=True: the Monte-Carlo form would draw the '
                       'cached sample from the prior, which has none')
+    if not reverse and self.latent_cov == 'tril':
+      raise NotImplementedError("latent_cov='tril' with reverse=False: KL(p || q) needs the inverse of L")
     self.analytic = 2 if not reverse else int(bool(analytic))
 
   def n_params_end(self) -> int:
@@ -1589,6 +1646,12 @@ class VAEEngine:
     if eps is None:
       lib.odin_rng_normal(self.eps.data_ptr(), B * D, self.seed, self.hp(N_HYPER), st)
     h_e = self.enc.forward(x, st)
+    if self.latent_cov == 'tril':
+      lib.odin_dense_fwd_ranged(h_e.data_ptr(), lw.data_ptr(), lb.data_ptr(), self.p.data_ptr(), B, self.hdim, self.pw,
+                                0, self._tril_x_word, None, st)
+      lib.odin_latent_tril_fwd(self.p.data_ptr(), self.eps.data_ptr(), self.z.data_ptr(), self.kl.data_ptr(),
+                               self.fbmask.data_ptr(), B, D, int(self.analytic), self.free_bits, cap, st)
+      return self.z, 0
     lib.odin_dense_fwd(h_e.data_ptr(), lw.data_ptr(), lb.data_ptr(), self.p.data_ptr(), B,
                        self.hdim, 2 * D, 0, st)
     lib.odin_latent_fwd(self.p.data_ptr(), self.eps.data_ptr(), self.z.data_ptr(),
@@ -1926,6 +1989,23 @@ class VAEEngine:
                                 int(self.analytic), self.enc.set_top_word(True), st)
       jobs.append(self._slab_job(self.lb_slab0, r0.w_off, self.lb_rows))
       jobs.append(self._slab_job(self.lb_slabl, self.lat_w_off, self.lb_rows))
+    elif self.latent_cov == 'tril':
+      # dp with its range word, then the projection's two gradients as ONE call (as NetProgram.backward's Dense layers)
+      lib.odin_latent_tril_bwd(self.p.data_ptr(), self.eps.data_ptr(), self.z.data_ptr(), self.dz.data_ptr(), dzx,
+                               self.fbmask.data_ptr(), self.hp(H_KLW), self.dp.data_ptr(), self._tril_dp_word, B, D,
+                               int(self.analytic), st)
+      rows, wrows = C.c_int(0), C.c_int(0)
+      auxp = h_e.data_ptr() if aux_act != 0 else None
+      bslab = self.enc.bslabs[-1]
+      top = self.enc.set_top_word(True)
+      lib.odin_dense_bwd_ranged(h_e.data_ptr(), self.dp.data_ptr(), lw.data_ptr(), auxp, aux_act,
+                                self.enc.gouts[-1].data_ptr(), bslab.data_ptr() if bslab is not None else None,
+                                C.byref(rows), self.lat_slab.data_ptr(), C.byref(wrows), B, self.hdim, self.pw, 1, 1,
+                                self._tril_dp_word, top, self._tril_x_word, st)
+      assert 0 < wrows.value <= self.lat_rows
+      jobs.append(self._slab_job(self.lat_slab, self.lat_w_off, wrows.value))
+      if bslab is not None:
+        jobs.append(self._slab_job(bslab, last.b_off, rows.value))
     else:
       lib.odin_latent_bwd(self.p.data_ptr(), self.eps.data_ptr(), self.z.data_ptr(),
                           self.dz.data_ptr(), dzx, self.fbmask.data_ptr(), self.hp(H_KLW), tl, ts,

@@ -50,6 +50,11 @@ class RVconf:
   name: str = 'latents'
   kwargs: dict = field(default_factory=dict)
 
+  def __post_init__(self):
+    # (the reference takes a bare int too: RVconf(5, 'mvntril', ...))
+    if isinstance(self.event_shape, int):
+      self.event_shape = (int(self.event_shape),)
+
   @property
   def event_size(self) -> int:
     n = 1

@@ -53,6 +53,8 @@ class KLdivergence:
     if not reverse and not analytic:
       raise TypeError('reverse=False needs analytic=True (helpers.py:261-276: the swapped '
                       '"posterior" is the prior, which carries no cached sample)')
+    if isinstance(q, MVNTriLPosterior):
+      return self._tril(q, analytic, reverse, free_bits, keepdims)
     if not reverse:  # KL(p || q), helpers.py:261-265
       kl = (torch.log(q.scale) + 0.5 * (1.0 + q.loc ** 2) / q.scale ** 2 - 0.5).sum(-1)
     elif analytic:
@@ -66,6 +68,24 @@ class KLdivergence:
       kl = torch.clamp(kl, min=free_bits * q.loc.shape[-1])
     if analytic and keepdims:
       kl = kl.unsqueeze(0)  # odin/bay/helpers.py:370-371
+    return kl
+
+  @staticmethod
+  def _tril(q: 'MVNTriLPosterior', analytic, reverse, free_bits, keepdims):
+    if not reverse:
+      raise NotImplementedError("'mvntril' with reverse=False: KL(p || q) needs the inverse of L")
+    D = q.loc.shape[-1]
+    logdet = torch.log(torch.diagonal(q.scale_tril, dim1=-2, dim2=-1)).sum(-1)
+    if analytic:
+      # (TFP registers no KL between MultivariateNormalTriL and Independent(Normal): the closed form is the evident
+      # intent -- DESIGN 3.15)
+      kl = 0.5 * ((q.scale_tril ** 2).sum((-2, -1)) + (q.loc ** 2).sum(-1) - D) - logdet
+    else:
+      kl = q.log_prob(q.z) - (-0.5 * (q.z ** 2).sum(-1) - 0.5 * D * LOG2PI)
+    if free_bits is not None:
+      kl = torch.clamp(kl, min=free_bits * D)
+    if analytic and keepdims:
+      kl = kl.unsqueeze(0)
     return kl
 
 
@@ -99,6 +119,65 @@ class MVNDiagPosterior:
   def log_prob(self, z):
     D = self.loc.shape[-1]
     return (-0.5 * ((z - self.loc) / self.scale) ** 2 - torch.log(self.scale)).sum(-1) \
+        - 0.5 * D * LOG2PI
+
+  def __array__(self):
+    return self.z.detach().cpu().numpy()
+
+  def tensor(self):
+    """tf.convert_to_tensor(q): the cached sample."""
+    return self.z
+
+
+TRIL_DIAG_SHIFT = 1e-5   # FillScaleTriL's diag_shift (continuous.py:465-469)
+
+
+def fill_scale_tril(r: torch.Tensor, D: int) -> torch.Tensor:
+  """tfb.FillScaleTriL(diag_bijector=softplus, diag_shift=1e-5): r [..., D (D + 1) / 2] -> L [..., D, D].  r[D:] followed
+  by r reversed are D * D values, read row-major as a D x D matrix of which the lower triangle is kept."""
+  m = torch.cat([r[..., D:], torch.flip(r, dims=(-1,))], -1).reshape(tuple(r.shape[:-1]) + (D, D))
+  d = torch.nn.functional.softplus(torch.diagonal(m, dim1=-2, dim2=-1)) + TRIL_DIAG_SHIFT
+  return torch.tril(m, -1) + torch.diag_embed(d)
+
+
+class MVNTriLPosterior:
+  """MultivariateNormalTriL(loc, FillScaleTriL(raw)) with its cached sample (odin/bay/layers/continuous.py:459-474,
+  covariance='tril'); p [B, D + D (D + 1) / 2] = (loc | raw)."""
+
+  def __init__(self, p: torch.Tensor, z: torch.Tensor, D: int):
+    self.loc = p[:, :D]
+    self.raw_scale = p[:, D:]
+    self.scale_tril = fill_scale_tril(self.raw_scale, D)
+    self.z = z
+    self.KL_divergence = KLdivergence(self)
+
+  event_shape = property(lambda self: (self.loc.shape[-1],))
+  batch_shape = property(lambda self: tuple(self.loc.shape[:-1]))
+
+  def mean(self):
+    return self.loc
+
+  def stddev(self):
+    """sqrt of the covariance's diagonal: the row norms of L"""
+    return torch.sqrt((self.scale_tril ** 2).sum(-1))
+
+  def covariance(self):
+    return self.scale_tril @ self.scale_tril.transpose(-1, -2)
+
+  def sample(self, n=None, seed=None):
+    g = None
+    if seed is not None:
+      g = torch.Generator(device=self.loc.device).manual_seed(int(seed))
+    shp = tuple(self.loc.shape) if n is None else (int(n),) + tuple(self.loc.shape)
+    e = torch.randn(shp, device=self.loc.device, generator=g)
+    return self.loc + (self.scale_tril @ e.unsqueeze(-1)).squeeze(-1)
+
+  def log_prob(self, z):
+    D = self.loc.shape[-1]
+    d = (z - self.loc).unsqueeze(-1)
+    L = self.scale_tril.expand(tuple(d.shape[:-2]) + (D, D))
+    e = torch.linalg.solve_triangular(L, d, upper=False).squeeze(-1)   # (host-side solve: L e = z - loc)
+    return -0.5 * (e ** 2).sum(-1) - torch.log(torch.diagonal(self.scale_tril, dim1=-2, dim2=-1)).sum(-1) \
         - 0.5 * D * LOG2PI
 
   def __array__(self):
@@ -329,9 +408,16 @@ class VariationalAutoencoder:
     for n, net in (('encoder', encoder), ('decoder', decoder)):
       if not isinstance(net, SequentialNetwork):
         raise ValueError(f'{n} must be a SequentialNetwork description, got {type(net)}')
-    if latents.posterior not in ('mvndiag', 'diag', 'normaldiag'):
+    posterior = latents.posterior
+    if posterior not in ('mvndiag', 'diag', 'normaldiag', 'mvntril', 'tril'):
       raise ValueError(f"latents posterior {latents.posterior!r} is outside the HIP path "
-                       f"(supported: 'mvndiag')")
+                       f"(supported: 'mvndiag', 'mvntril')")
+    self._latent_cov = 'tril' if posterior in ('mvntril', 'tril') else 'diag'
+    if self._latent_cov == 'tril':
+      if self._tril_refusal is not None:
+        raise ValueError(f"{type(self).__name__} with a 'mvntril' posterior: {self._tril_refusal}")
+      if not reverse:
+        raise NotImplementedError("'mvntril' with reverse=False: KL(p || q) needs the inverse of L")
     sample_shape = (sample_shape,) if isinstance(sample_shape, int) else tuple(sample_shape)
     if len(sample_shape) > 1:
       raise ValueError(f'sample_shape={sample_shape}: at most one sample axis')
@@ -382,7 +468,7 @@ class VariationalAutoencoder:
                       tc=self._tc_mode, capacity=self._capacity_mode,
                       lib=self._lib, params=self._params, seed=self.seed + self._rank(),
                       optim_state=self._optim_state, world_size=self._world_size(),
-                      force_dp=bool(getattr(self, 'force_dp', False)),
+                      force_dp=bool(getattr(self, 'force_dp', False)), latent_cov=self._latent_cov,
                       **self._reg_options(), **getattr(self, 'engine_options', {}))
       if self._params is None:
         self._params = eng.params
@@ -445,6 +531,8 @@ class VariationalAutoencoder:
 
   def set_elbo_configs(self, analytic=None, reverse=None, free_bits=None, sample_shape=None):
     """odin/bay/vi/_base.py:51-89"""
+    if reverse is not None and not reverse and self._latent_cov == 'tril':
+      raise NotImplementedError("'mvntril' with reverse=False: KL(p || q) needs the inverse of L")
     if analytic is not None:
       self.analytic = bool(analytic)
     if reverse is not None:
@@ -495,9 +583,13 @@ class VariationalAutoencoder:
   def _reg_options(self) -> dict:
     return {}
 
+  # why a model class cannot take the full-covariance posterior ('mvntril'); None: it can
+  _tril_refusal: Optional[str] = None
+
   # ------------------------------------------------------------------ forward API
-  def _posterior(self, eng: VAEEngine) -> MVNDiagPosterior:
-    return MVNDiagPosterior(eng.p.clone(), eng.z.clone(), eng.D)
+  def _posterior(self, eng: VAEEngine) -> Union[MVNDiagPosterior, MVNTriLPosterior]:
+    cls = MVNTriLPosterior if self._latent_cov == 'tril' else MVNDiagPosterior
+    return cls(eng.p.clone(), eng.z.clone(), eng.D)
 
   def _observation_dist(self, h: torch.Tensor):
     if self.observation.posterior == 'bernoulli':
@@ -521,7 +613,7 @@ class VariationalAutoencoder:
 
   def decode(self, latents, training=None, mask=None, only_decoding=False, **kwargs):
     """variational_autoencoder.py:316-360"""
-    z = latents.tensor() if isinstance(latents, MVNDiagPosterior) else latents
+    z = latents.tensor() if isinstance(latents, (MVNDiagPosterior, MVNTriLPosterior)) else latents
     z = _as_tensor(z, self.device)
     eng = self._engine(z.shape[0])
     h = eng.run_decoder(z).clone()
@@ -607,8 +699,9 @@ class VariationalAutoencoder:
         e = _as_tensor(eps, self.device)[:, i0:i0 + B].contiguous()
       z = torch.empty(n, B, D, **f32)
       lq, lp, llk = torch.empty(n, B, **f32), torch.empty(n, B, **f32), torch.empty(n, B, **f32)
-      lib.odin_latent_sample_logprob(eng.p.data_ptr(), e.data_ptr(), z.data_ptr(), lq.data_ptr(),
-                                     lp.data_ptr(), n, B, D, st)
+      sample_logprob = (lib.odin_latent_tril_sample_logprob if self._latent_cov == 'tril'
+                        else lib.odin_latent_sample_logprob)
+      sample_logprob(eng.p.data_ptr(), e.data_ptr(), z.data_ptr(), lq.data_ptr(), lp.data_ptr(), n, B, D, st)
       self._prior_log_prob(eng, z, lp)
       # decode the n*B codes in chunks of whole sample-rows (bounded activation memory)
       rows = max(1, min(n, 2048 // max(B, 1)))
@@ -1018,6 +1111,8 @@ class BetaTCVAE(BetaVAE):
   """beta_vae.py:110-129: + (beta-1) * total_correlation(z, q(z|x)) (losses.py:101-157);
   the KL is ALSO scaled by beta through BetaVAE.elbo_components (:42)."""
 
+  _tril_refusal = 'the total-correlation estimator reads a diagonal scale'
+
   def __init__(self, beta: float = 1.0, name='BetaTCVAE', **kwargs):
     super().__init__(beta=beta, name=name, **kwargs)
     self._tc_mode = 'betatc'
@@ -1075,6 +1170,7 @@ class DIPVAE(BetaVAE):
     super().__init__(beta=beta, name=name, **kwargs)
 
   _reg_key = 'dip'
+  _tril_refusal = 'the disentangled-inferred-prior penalty reads a diagonal scale'
 
   def _reg_options(self) -> dict:
     return dict(latent_reg='dip_i' if self.only_mean else 'dip_ii', reg_coef=1.0,
@@ -1149,6 +1245,8 @@ class VampriorVAE(BetaVAE):
   kl['kl_<latents>'] = beta * (kl_std + c).  `pseudoinputs`: an explicit [n_components, prod(input_shape)] array for
   W_u (the reference's Vamprior takes it; its VampriorVAE does not pass it on).  Not offered with this prior:
   analytic / forward KL, free_bits, sample_shape other than (), data parallelism."""
+
+  _tril_refusal = "the mixture's components read a diagonal scale"
 
   def __init__(self, n_components: int = 500, pseudoinputs_mean: float = -0.05, pseudoinputs_std: float = 0.01,
                beta: Union[float, Interpolation] = linear(vmin=1e-6, vmax=1., steps=2000, delay_in=0),
@@ -1316,6 +1414,8 @@ class VQVAE(BetaVAE):
   returns them and the step is the one VQVAEStep describes.  `code_size=None`: one code per input
   (what the reference does with the image networks).  Not offered: analytic=False (ValueError, as the reference),
   free_bits, sample_shape other than (), marginal_log_prob (the posterior has no density), data parallelism."""
+
+  _tril_refusal = 'the quantised latent has no Gaussian posterior'
 
   def __init__(self, n_codes: int = 64, commitment_weight: float = 0.25, distance_metric: str = 'euclidean',
                trainable_prior: bool = False, ema_decay: float = 0.99, ema_update: bool = False,
@@ -1554,6 +1654,8 @@ class FactorVAE(AnnealingVAE):
             D(permute_dims(z')) with z' = encode(x2) (factor_discriminator.py:200-235).
   On one GPU the whole iteration (both steps, both optimisers) is replayed as ONE HIP graph
   when `use_graph` / `fit(compile_graph=True)`."""
+
+  _tril_refusal = 'its forward-only second engine shares range words, which the triangular path does not offer'
 
   def __init__(self, discriminator_units: Sequence[int] = (1000,) * 5, discriminator_optim=None,
                activation: str = 'relu', batchnorm: bool = False, tc_coef: float = 7.0,
