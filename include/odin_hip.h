@@ -183,6 +183,22 @@ int odin_bernoulli_tail_fwd_bwd(int is_deconv, const float* x, const float* w, c
                                 float* tail_slab, int* slab_rows_out, const float* scale,
                                 const odin_conv_desc* d, int C1, void* stream);
 
+/* ---- the same tail with the Conv2DTranspose BELOW it in the same launch (tconv_planes.hip: tconv_chain2_kernel): d3 =
+ * Conv2DTranspose(k4, s2, ELU) [B,16,16,64] -> y3 [B,32,32,32] (decoder3 of the 64 x 64 image stacks; x, w3, b3; d3->x_amax
+ * optional, d3->y_amax optional: receives the word of y3 as odin_deconv2d_fwd leaves it), d4 = the tail's layer on y3
+ * (w4, b4; d4->dy_amax as in odin_bernoulli_tail_fwd_bwd; d4->x_amax is not read).  The forward pass couples no
+ * samples: a workgroup owns whole images, runs d3 for them and goes straight on to the tail for the same images.
+ * y3, logits and g_out are what the two calls compute, bit for bit; llk_part, the slab rows and the word of g_out
+ * depend on the partition as they do in the tail itself: *same_partition_out = 1 where the chain's partition is that
+ * of odin_bernoulli_tail_fwd_bwd -- then they are bit-identical too (provided the bound of every workgroup's part of y3
+ * lies inside [2^-8, 2^15) whenever the batch's does: the tail scales y3 by its OWN images' bound).
+ * y3 == NULL = dry run (n_part, rows, same_partition).  -2: shapes outside the chain, the plane kernels switched off. */
+int odin_decoder_tail_chain(const float* x, const float* w3, const float* b3, float* y3, const odin_conv_desc* d3,
+                            const float* w4, const float* b4, const float* w1, const float* b1, const float* target,
+                            float* logits, float* g_out, float* llk_part, int* n_part_out, float* tail_slab,
+                            int* slab_rows_out, int* same_partition_out, const float* scale, const odin_conv_desc* d4,
+                            int C1, void* stream);
+
 /* ---- Dense (keras Dense: base_networks.py:1002-1014; DistributionDense projection:
  * odin/bay/layers/dense_distribution.py:229-238) ------------------------------------- */
 int odin_dense_fwd(const float* x, const float* w, const float* bias, float* y, int B, int K,

@@ -91,6 +91,7 @@ SIGNATURES = {
     'odin_deconv2d_dgrad': [P, P, P, I, P, P, IP, DP, P],
     'odin_deconv2d_wgrad': [P, P, P, IP, DP, P],
     'odin_bernoulli_tail_fwd_bwd': [I, P, P, P, P, P, P, P, P, P, IP, P, IP, P, DP, I, P],
+    'odin_decoder_tail_chain': [P, P, P, P, DP, P, P, P, P, P, P, P, P, IP, P, IP, IP, P, DP, I, P],
     'odin_dense_fwd': [P, P, P, P, I, I, I, I, P],
     'odin_dense_fwd_ranged': [P, P, P, P, I, I, I, I, P, P, P],
     'odin_dense_dgrad': [P, P, P, I, P, P, IP, I, I, I, P],

@@ -494,6 +494,21 @@ extern "C" int odin_bernoulli_tail_fwd_bwd(int is_deconv, const float* x, const 
   // (the range contract: a word handed in as d->dy_amax bounds g_out on return)
   return keep_range(rc, f, FOLDS_Y, g_out, (size_t)d->B * d->OH * d->OW * d->Cout, d->dy_amax, stream);
 }
+// the tail with the Conv2DTranspose below it in the same launch: only where BOTH layers are the plane kernels' (the
+// selectors' answer, so that every switch that turns those off turns the chain off too)
+extern "C" int odin_decoder_tail_chain(const float* x, const float* w3, const float* b3, float* y3, const odin_conv_desc* d3,
+                                       const float* w4, const float* b4, const float* w1, const float* b1,
+                                       const float* target, float* logits, float* g_out, float* llk_part, int* n_part_out,
+                                       float* tail_slab, int* slab_rows_out, int* same_partition_out, const float* scale,
+                                       const odin_conv_desc* d4, int C1, void* stream) {
+  const odin_geom g3 = odin_geom_fwd(d3), g4 = odin_geom_fwd(d4);
+  if (select_deconv2d_fwd(g3, true, d3->act) != TCONV_PLANES || select_bernoulli_tail(1, g4, d4->act, C1) != TCONV_PLANES ||
+      !odin_tconv_chain2_applicable(g3, g4, C1))
+    return odin_fail(-2, "decoder_tail_chain: shapes outside the chain");
+  return odin_tconv_chain2_launch(x, w3, b3, y3, w4, b4, w1, b1, target, logits, g_out, llk_part, n_part_out, tail_slab,
+                                  slab_rows_out, same_partition_out, scale, C1, d3->B, d3->x_amax, d3->y_amax, d4->dy_amax,
+                                  stream);
+}
 // 1: the fused tail folds max|g_out| into d->dy_amax itself
 extern "C" int odin_bernoulli_tail_keeps_range(int is_deconv, const odin_conv_desc* d, int C1) {
   return (traits(select_bernoulli_tail(is_deconv, odin_geom_fwd(d), d->act, C1)) & FOLDS_Y) ? 1 : 0;

@@ -175,6 +175,13 @@ int odin_tconv_planes_launch(const float* in, const float* w, const float* bias,
                              int CO, int epi, const uint32_t* in_amax, uint32_t* out_amax, void* stream);
 // the data gradient of the SECOND layer of the image stacks, which also forms the FIRST layer's weight gradient from the
 // dx tile it holds (g: the upper layer's data-gradient gather, l0: the first layer's forward gather); out may be null
+// Conv2DTranspose(64 -> 32) on 16-pixel rows -> the fused Bernoulli tail, one launch (g3, g4: the two forward gathers)
+bool odin_tconv_chain2_applicable(const odin_geom& g3, const odin_geom& g4, int C1);
+int odin_tconv_chain2_launch(const float* x, const float* w3, const float* b3, float* y3, const float* w4, const float* b4,
+                             const float* w1, const float* b1, const float* target, float* logits, float* g_out,
+                             float* llk_part, int* n_part_out, float* slab, int* rows_out, int* same_partition_out,
+                             const float* scale, int C1, int B, const uint32_t* x_amax, uint32_t* y3_amax,
+                             uint32_t* dy_amax, void* stream);
 bool odin_tconv_planes_first_applicable(const odin_geom& g, const odin_geom& l0);
 int odin_tconv_planes_first_launch(const float* in, const float* w, const float* aux, float* out, float* colsum, const float* img,
                                    int center0, float* wslab0, int* rows_out, int B, const uint32_t* in_amax,

@@ -130,6 +130,46 @@ constexpr int TP_FW_IMG_FLOATS = 18 * TP_FW_IMG_STRIDE;  // the 18 image rows un
 constexpr int TP_FW_BYTES = 8 * 4096 + TP_FW_IMG_FLOATS * 4;   // stage + patch (the 16 chains' partials overlay them)
 static_assert(16 * 17 * 32 * 4 <= TP_FW_BYTES, "the partials of the 16 chains overlay the stage and the patch");
 
+// Where a body runs.  The stand-alone kernels take it from blockIdx (tp_here); a chain kernel (below) runs several
+// bodies for the same images and hands every one its channel block and tile range.  in_local / out_local (chains
+// only, LDS words): the bound of THIS workgroup's part of the input / the word that receives the maximum over this
+// workgroup's part of `out` -- the global word of a tensor is not complete while other workgroups still produce it.
+struct TpAt {
+  int n0;                    // first output channel of the body's 32
+  int T0;                    // first tile
+  int row;                   // row of the workgroup in colsum / slab / wslab0; < 0: blockIdx.x (taken where it is used)
+  int slot;                  // sub-word of the range word the workgroup commits to; < 0: by blockIdx as ever
+  const unsigned* in_local;
+  unsigned* out_local;
+};
+
+// a value every lane of the wave holds, for the scalar unit
+__device__ __forceinline__ unsigned tp_uniform(unsigned v) {
+#ifdef ODIN_SIM
+  return v;
+#else
+  return __builtin_amdgcn_readfirstlane(v);
+#endif
+}
+// the stand-alone kernels: channel block blockIdx.y, tiles and rows by blockIdx.x
+__device__ __forceinline__ TpAt tp_here(const TPParams& p) {
+  return TpAt{(int)blockIdx.y * 32, (int)blockIdx.x * p.tiles_per_wg, -1, -1, nullptr, nullptr};
+}
+// odin_amax_commit_wg that also folds the workgroup's maximum into an LDS word of the workgroup (chains)
+__device__ __forceinline__ void tp_amax_commit_local(unsigned* block, unsigned* local, float amx, int tid, float* red,
+                                                     unsigned wg) {
+  const float m = odin_wave_max64(amx);
+  if ((tid & 63) == 0) red[tid >> 6] = m;
+  __syncthreads();
+  if (tid == 0) {
+    float t = red[0];
+    for (int w = 1; w < 8; ++w) t = fmaxf(t, red[w]);
+    const unsigned b = odin_fbits(t);
+    if (block != nullptr) atomicMax(block + (wg & (ODIN_RANGE_SLOTS - 1)) * ODIN_RANGE_STRIDE, b);
+    if (b > *local) *local = b;
+  }
+}
+
 struct TpItem {
   float4 v;
   int dst;  // byte offset of the hi-plane store inside the ring
@@ -160,7 +200,7 @@ struct TpItem {
 // stage and the patch for the next epilogue.  fp32 products: dx has no range word before the launch ends, and the kernel this
 // replaces is IEEE fp32.
 template <int EPI, int C1, int W, int DBG = 0, bool ACC = false, int SCM = 0, bool PL = false, bool FW = false>
-__device__ __forceinline__ void tp_body(const TPParams& p) {
+__device__ __forceinline__ void tp_body(const TPParams& p, const TpAt at) {
   static_assert(!FW || (EPI == 2 && W == 16 && C1 == 1 && !ACC && !PL), "FW: the 32-channel data gradient, 16-pixel rows");
   constexpr int NPL = TP_NPL;
   constexpr int RP = 64 / W;              // input rows per tile
@@ -191,15 +231,16 @@ __device__ __forceinline__ void tp_body(const TPParams& p) {
     p.stamps[65] = wall_clock64();
   }
 #endif
-  const int n0 = blockIdx.y * 32;
+  const int n0 = at.n0;
+  auto wg_row = [&] { return at.row < 0 ? (size_t)blockIdx.x : (size_t)at.row; };
   const int HP = p.H + 1;
   const int OH = 2 * p.H, OW = 2 * W;
-  const int T0 = blockIdx.x * p.tiles_per_wg;
+  const int T0 = at.T0;
   int T1 = T0 + p.tiles_per_wg;
   if (T1 > p.n_tiles) T1 = p.n_tiles;
   if (T0 >= T1) return;
 
-  const OdinRangeReq in_rq = odin_range_issue(SCM != 0 ? p.in_amax : nullptr, lane);   // (finished behind the prologue's loads)
+  const OdinRangeReq in_rq = odin_range_issue((SCM != 0 && at.in_local == nullptr) ? p.in_amax : nullptr, lane);   // (finished behind the prologue's loads)
   // ---- the loads of the prologue go out FIRST: the 8 weight loads of a thread (fp32 [tap][co][32]) and the wave's
   // items of fill 0 (all rows of tile T0, offsets computed directly) are in flight while the zero fills and the table
   // arithmetic run -- the layers with 8- and 16-pixel rows run only 1-4 tiles per workgroup ----
@@ -392,7 +433,7 @@ __device__ __forceinline__ void tp_body(const TPParams& p) {
   // ring (both loaded at the top of the kernel), then ONE barrier publishes them together with the pads and the table
   if (SCM != 0) {
     // the input's range word (requested first thing in the kernel): the bound, the scale flag, the powers of two
-    const unsigned in_mb = odin_range_finish(in_rq);
+    const unsigned in_mb = at.in_local != nullptr ? tp_uniform(*at.in_local) : odin_range_finish(in_rq);
     scl = SCM == 1 || odin_act_needs_scale(in_mb);
     const int gk = scl ? odin_range_shift(in_mb) : 0;
     in_s = odin_pow2(gk); in_s2k = odin_pow2(gk + 11);
@@ -877,7 +918,7 @@ __device__ __forceinline__ void tp_body(const TPParams& p) {
 #pragma unroll
       for (int c = 0; c < 16; c += 4)
         tt += (part[c * 544 + e] + part[(c + 1) * 544 + e]) + (part[(c + 2) * 544 + e] + part[(c + 3) * 544 + e]);
-      p.wslab0[(size_t)blockIdx.x * (17 * 32) + e] = tt;
+      p.wslab0[wg_row() * (17 * 32) + e] = tt;
     }
   }
 
@@ -889,7 +930,9 @@ __device__ __forceinline__ void tp_body(const TPParams& p) {
 #endif
   if (EPI >= 1) {   // (EPI 1: the range word of the activation, odin_conv_desc.y_amax; EPI 2 / 3: of the gradient)
     __syncthreads();
-    odin_amax_commit_wg(p.out_amax, amx, tid, 512, cred, blockIdx.x + gridDim.x * blockIdx.y);
+    const unsigned slot = at.slot < 0 ? blockIdx.x + gridDim.x * blockIdx.y : (unsigned)at.slot;
+    if (at.out_local != nullptr) tp_amax_commit_local(p.out_amax, at.out_local, amx, tid, cred, slot);
+    else odin_amax_commit_wg(p.out_amax, amx, tid, 512, cred, slot);
     __syncthreads();  // (cred is reused below)
   }
   // ---- per-workgroup partial sums: 32 pixel lanes by shuffles, then the 8 waves through LDS ----
@@ -926,7 +969,7 @@ __device__ __forceinline__ void tp_body(const TPParams& p) {
     if (tid < 32) {
       float tt = 0.f;
       for (int wv = 0; wv < 8; ++wv) tt += cred[wv * NRED + tid];
-      p.colsum[(size_t)blockIdx.x * p.CO + n0 + tid] = tt;
+      p.colsum[wg_row() * p.CO + n0 + tid] = tt;
     }
   }
   if (EPI == 3) {
@@ -936,7 +979,7 @@ __device__ __forceinline__ void tp_body(const TPParams& p) {
       p.llk_part[T1 - 1] = ((q[0] + q[1]) + (q[2] + q[3])) + ((q[4] + q[5]) + (q[6] + q[7]));
     }
     // slab row: [dW1 (CO, C1) | db1 (C1) | column sums of out (CO)]
-    float* row = p.slab + (size_t)blockIdx.x * (p.CO * C1 + C1 + p.CO);
+    float* row = p.slab + wg_row() * (p.CO * C1 + C1 + p.CO);
     for (int e = tid; e < 32 + 32 * C1 + C1; e += 512) {
       float tt = 0.f;
       for (int wv = 0; wv < 8; ++wv) tt += cred[wv * NRED + e];
@@ -954,7 +997,7 @@ __device__ __forceinline__ void tp_body(const TPParams& p) {
 
 template <int EPI, int C1, int W, int DBG = 0, bool ACC = false, int SCM = 0, bool FW = false>
 __global__ __launch_bounds__(512) void tconv_planes_kernel(TPParams p) {
-  tp_body<EPI, C1, W, DBG, ACC, SCM, false, FW>(p);
+  tp_body<EPI, C1, W, DBG, ACC, SCM, false, FW>(p, tp_here(p));
 }
 
 // 64 reduction channels in ONE launch: both 32-channel passes inside the kernel (round 3 launched them separately: a
@@ -969,7 +1012,7 @@ __global__ __launch_bounds__(512) void tconv_planes2_kernel(TPParams p) {
     q.colsum = nullptr;
     q.out_amax = nullptr;
     q.ci_off = 0;
-    tp_body<0, 1, W, 0, false, SCM, PL>(q);
+    tp_body<0, 1, W, 0, false, SCM, PL>(q, tp_here(q));
   }
   // (the same thread reads back what it wrote, through the same CU's write-through L1 and its XCD's L2: a
   // workgroup-scope fence orders it; a device-scope __threadfence() writes back and invalidates the whole L2 of the
@@ -980,7 +1023,49 @@ __global__ __launch_bounds__(512) void tconv_planes2_kernel(TPParams p) {
 #endif
   __syncthreads();
   p.ci_off = 32;
-  tp_body<EPI, 1, W, 0, true, SCM, PL>(p);
+  tp_body<EPI, 1, W, 0, true, SCM, PL>(p, tp_here(p));
+}
+
+// Chain of two sample-local forward layers in ONE launch: Conv2DTranspose(64 -> 32, k4, s2) on 16-pixel rows (decoder3 of
+// the 64 x 64 image stacks) and the fused Bernoulli tail that reads its output.  No sample couples to another in the
+// forward pass, so a workgroup owns `ipw` whole images in BOTH stages: it runs the first layer for them (the two
+// reduction passes of tconv_planes2_kernel over all its tiles) and goes straight on to the tail for the same images,
+// reading its own part of y3 back through its CU's L1 / its XCD's L2 moments after writing it: no device-wide launch
+// boundary, no wait for the stragglers of the first layer, no cold start of the tail's row fills.  The first pass's raw
+// partial sums travel through y3 itself (the non-PL form: the SAME thread reads them back): with them in LDS only two of
+// an image's four tiles fit, the pass pair ran twice per image with four prologues instead of two, and the launch
+// measured 88.0 us against 81.0 us this way (the two launches: 29.5 + 60.0; profiles/chain_kernel_stats_*.txt) -- here
+// the partial sums of an image are re-read by the CU that wrote them and never wait for HBM.
+// Between stages: the sequence between the two passes above (every wave's stores are acknowledged, workgroup-scope
+// fence, barrier) -- all a workgroup reads was written by itself; no workgroup waits for another.  The tail decides
+// whether to scale y3 from the maximum over THIS workgroup's part of y3 (y_local): the global word is still written
+// for the backward kernels, but it is complete only when the launch ends.
+// Results: y3 does not depend on the partition; the tail's slab rows, llk_part and range word do as they do
+// stand-alone, and where pt.tiles_per_wg equals the stand-alone tail's the launch is bit-identical to the two (as long
+// as every workgroup's bound of y3 lies on the same side of the safe window as the batch's).
+template <int C1>
+__global__ __launch_bounds__(512) void tconv_chain2_kernel(TPParams p3, TPParams pt) {
+  __shared__ unsigned y_local;
+  if (threadIdx.x == 0) y_local = 0u;   // (published by the barriers of the first body)
+  auto stage_sync = [] {
+    odin_wait_vmem();
+#ifndef ODIN_SIM
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+#endif
+    __syncthreads();
+  };
+  const int T3 = (int)blockIdx.x * p3.tiles_per_wg;   // (a body clips its tile range to n_tiles)
+  {
+    TPParams q = p3;
+    q.out_amax = nullptr;
+    q.ci_off = 0;
+    tp_body<0, 1, 16, 0, false, 2, false>(q, TpAt{0, T3, 0, 0, nullptr, nullptr});
+  }
+  stage_sync();
+  p3.ci_off = 32;
+  tp_body<1, 1, 16, 0, true, 2, false>(p3, TpAt{0, T3, 0, (int)blockIdx.x, nullptr, &y_local});
+  stage_sync();
+  tp_body<3, C1, 32, 0, false, 2>(pt, TpAt{0, (int)blockIdx.x * pt.tiles_per_wg, (int)blockIdx.x, (int)blockIdx.x, &y_local, nullptr});
 }
 
 // LDS: weight planes + row ring + the fill table (rows per fill x 8 bytes per fill, tiles + 3 fills); 4.3 KB are static
@@ -1101,7 +1186,77 @@ int tp_launch2_w(const TPParams& p0, int W, dim3 grid, void* stream) {
   return odin_check_launch("tconv_planes(f16x2)");
 }
 
+// the chain's partition: whole images per workgroup, the chip filled once
+int tp_chain_ipw(int B) {
+  int cap = odin_num_cus();
+  if (cap > ODIN_MAX_COLSUM_BLOCKS) cap = ODIN_MAX_COLSUM_BLOCKS;
+  if (cap < 1) cap = 1;
+  return (B + cap - 1) / cap;
+}
+
+template <int C1>
+int tp_launch_chain2(const TPParams& p3, const TPParams& pt, int gx, size_t lds, void* stream) {
+#ifndef ODIN_SIM
+  // (what the launch needs: beyond the default 64 KB)
+  static size_t attr_lds = 0;
+  if (lds > attr_lds) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&tconv_chain2_kernel<C1>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+      (void)hipGetLastError();
+    attr_lds = lds;
+  }
+#endif
+  ODIN_LAUNCH((tconv_chain2_kernel<C1>), dim3(gx, 1, 1), dim3(512), lds, stream, p3, pt);
+  return odin_check_launch("tconv_chain2(f16x2)");
+}
+
 }  // namespace
+
+// ---- decoder3 forward -> fused Bernoulli tail in one launch (tconv_chain2_kernel) ----
+// g3: Conv2DTranspose 16 x 16 x 64 -> 32 x 32 x 32, g4: 32 x 32 x 32 -> 64 x 64 x 32, then the 1x1 head of C1 maps
+bool odin_tconv_chain2_applicable(const odin_geom& g3, const odin_geom& g4, int C1) {
+  if (!odin_tconv_planes_applicable(g3, 1, 1) || !odin_tconv_planes_applicable(g4, 3, C1)) return false;
+  if (g3.B != g4.B || g3.H != 16 || g3.W != 16 || g3.CI != 64 || g3.CO != 32 || g4.H != 32 || g4.W != 32 || g4.CI != 32 ||
+      g4.CO != 32)
+    return false;
+  // (the fill tables of both stages beside the weight planes and the ring)
+  const int ipw = tp_chain_ipw(g3.B);
+  return (size_t)tp_ring_bytes(32) + (size_t)(16 * ipw + 3) * tp_fill_bytes(32) <= (size_t)TP_LDS_MAX &&
+         (size_t)tp_ring_bytes(16) + (size_t)(4 * ipw + 3) * tp_fill_bytes(16) <= (size_t)TP_LDS_MAX;
+}
+
+// y3 == nullptr: dry run (rows, partials per sample, whether the tail's partition is the stand-alone launch's)
+int odin_tconv_chain2_launch(const float* x, const float* w3, const float* b3, float* y3, const float* w4, const float* b4,
+                             const float* w1, const float* b1, const float* target, float* logits, float* g_out,
+                             float* llk_part, int* n_part_out, float* slab, int* rows_out, int* same_partition_out,
+                             const float* scale, int C1, int B, const uint32_t* x_amax, uint32_t* y3_amax,
+                             uint32_t* dy_amax, void* stream) {
+  const int ipw = tp_chain_ipw(B), gx = (B + ipw - 1) / ipw;
+  if (rows_out) *rows_out = gx;
+  if (n_part_out) *n_part_out = 16;
+  if (same_partition_out) *same_partition_out = tp_tiles_per_wg(32, B * 16, 1) == 16 * ipw ? 1 : 0;
+  if (y3 == nullptr) return 0;
+  TPParams p3, pt;
+  memset(&p3, 0, sizeof(p3));
+  memset(&pt, 0, sizeof(pt));
+  p3.in = x; p3.w = w3; p3.bias = b3; p3.out = y3;
+  p3.B = B; p3.H = 16; p3.CO = 32; p3.CS = 64;
+  p3.tiles_per_img = 4; p3.n_tiles = 4 * B;
+  p3.tiles_per_wg = 4 * ipw;
+  p3.in_amax = x_amax; p3.out_amax = y3_amax;
+  const size_t lds3 = (size_t)tp_ring_bytes(16) + (size_t)(p3.tiles_per_wg + 3) * tp_fill_bytes(16);
+  pt.in = y3; pt.w = w4; pt.bias = b4; pt.out = g_out;
+  pt.w1 = w1; pt.b1 = b1; pt.target = target; pt.logits = logits; pt.llk_part = llk_part; pt.slab = slab; pt.scale = scale;
+  pt.B = B; pt.H = 32; pt.CO = 32; pt.CS = 32;
+  pt.tiles_per_img = 16; pt.n_tiles = 16 * B; pt.tiles_per_wg = 16 * ipw;
+  pt.out_amax = dy_amax;
+  const size_t ldst = (size_t)tp_ring_bytes(32) + (size_t)(pt.tiles_per_wg + 3) * tp_fill_bytes(32);
+  const size_t lds = lds3 > ldst ? lds3 : ldst;
+  if (lds > (size_t)TP_LDS_MAX) return odin_fail(-2, "tconv_chain2: LDS");
+  if (C1 == 1) return tp_launch_chain2<1>(p3, pt, gx, lds, stream);
+  if (C1 == 3) return tp_launch_chain2<3>(p3, pt, gx, lds, stream);
+  return odin_fail(-2, "tconv_chain2: one or three logit maps only");
+}
 
 static long long* g_tp_stamps = nullptr;
 void odin_tconv_planes_set_stamps(void* buf) { g_tp_stamps = (long long*)buf; }

@@ -522,7 +522,7 @@ class VAEEngine:
                pseudoinputs_std: float = 0.01, pseudoinputs=None,
                vq_codes: Optional[int] = None, vq_code_size: Optional[int] = None, vq_commitment: float = 0.25,
                vq_ema: bool = False, vq_ema_decay: float = 0.99, vq_epsilon: float = 1e-5, vq_state=None,
-               latent_cov: str = 'diag'):
+               latent_cov: str = 'diag', chain_fwd: bool = True):
     """The keyword-only arguments are the engine's launch-order / A-B options (tests and tools pass them; the engine
     reads no environment variable):
       act_words        activation range words for the two-plane consumers; False: unscaled planes
@@ -544,6 +544,10 @@ class VAEEngine:
                        Conv2DTranspose as ONE launch per direction where the shapes allow (neck.hip); False: round 5's
                        four launches per direction
       neck_bwd         the neck's backward launch (None: where it was measured faster)
+      chain_fwd        the Conv2DTranspose below the fused Bernoulli tail inside the tail's launch, a workgroup running both
+                       for its own images (odin_decoder_tail_chain) -- only where the library takes the
+                       shapes AND the chain's partition is the tail's own, so that the step's bits do not change; never in
+                       a data-parallel engine or under debug_check_ranges; False: the two launches
     The batch regularisers of InfoVAE / DIPVAE (latent_reg.hip; not combinable with `tc`):
       latent_reg         None | 'mmd' (maximum_mean_discrepancy of z against the prior) | 'dip_i' / 'dip_ii'
                          (disentangled_inferred_prior_loss with only_mean True / False); the term reg_coef * value is
@@ -739,6 +743,7 @@ class VAEEngine:
     if self.vq_K is None:
       self._plan_fused_tail(f32)
       self._plan_gauss_head(f32)
+      self._plan_chain_fwd(bool(chain_fwd))
       if latent_cov == 'tril':
         self._plan_tril(bool(act_words))
       else:
@@ -1124,6 +1129,7 @@ class VAEEngine:
   def _plan_vq(self, f32, own_params, vq_state):
     K, Cs, L, B = self.vq_K, self.vq_Cs, self.vq_L, self.B
     self.fused_tail, self.tail_mode = False, None
+    self.chain_tail = False
     self.gauss_head = self._used_head = False
     self.lat_block = self._used_block = False
     self.neck = self._used_neck = False
@@ -1252,6 +1258,27 @@ class VAEEngine:
     co, c1 = a.desc['Cout'], b.desc['Cout']
     self.tail_slab = torch.empty(rows.value, co * c1 + c1 + co, **f32)
     self.tail_llk_part = torch.empty(self.B * npart.value, **f32)
+
+  def _plan_chain_fwd(self, want: bool):
+    """decoder[-3] inside the fused Bernoulli tail's launch (odin_decoder_tail_chain) where the dry run takes the shapes
+    and reports the partition of the tail alone: same slab rows, same partials, same bits."""
+    self.chain_tail = False
+    recs = self.dec_recs
+    if not (want and self.fused_tail and self.tail_mode is None and not self.is_dp and len(recs) >= 3 and
+            recs[-3].kind == 'deconv' and recs[-2].kind == 'deconv'):
+      return
+    # (the library is asked only about the geometry the chain exists for: 16 x 16 x 64 -> 32 x 32 x 32 -> the tail)
+    d3 = recs[-3].desc
+    if (d3['H'], d3['W'], d3['Cin'], d3['Cout'], d3['K'], d3['stride']) != (16, 16, 64, 32, 4, 2):
+      return
+    rows, npart, same = C.c_int(0), C.c_int(0), C.c_int(0)
+    try:
+      self.lib.odin_decoder_tail_chain(None, None, None, None, C.byref(self.dec.descs[-3]), None, None, None, None, None,
+                                       None, None, None, C.byref(npart), None, C.byref(rows), C.byref(same), None,
+                                       C.byref(self.dec.descs[-2]), recs[-1].desc['Cout'], None)
+    except _lib.OdinError:   # (the library declines: other shapes, the plane kernels switched off)
+      return
+    self.chain_tail = bool(same.value) and rows.value == self.tail_rows and npart.value == self.tail_npart
 
   def _plan_gauss_tail(self, f32):
     """Training-step fusion Conv2DTranspose(k4, s2, 32 -> 32) -> Conv2D 1x1 (loc | scale) -> Normal log-prob + backward
@@ -1756,10 +1783,18 @@ class VAEEngine:
       h_d = self.dec.outs[-1]
     elif self.fused_tail and fused:
       nd = len(self.dec_recs)
-      h = self.dec.forward(dec_in, st, upto=nd - 2, start=dec_start)
+      chain = self.chain_tail and dec_start <= nd - 3 and not self.debug_check_ranges
+      h = self.dec.forward(dec_in, st, upto=nd - 3 if chain else nd - 2, start=dec_start)
       a, b = self.dec_recs[-2], self.dec_recs[-1]
       rows = C.c_int(0)
-      if self.tail_mode is not None:
+      if chain:
+        lib.odin_decoder_tail_chain(
+            h.data_ptr(), self.dec.w(nd - 3).data_ptr(), self.dec.b(nd - 3).data_ptr(), self.dec.outs[nd - 3].data_ptr(),
+            C.byref(self.dec.descs[nd - 3]), self.dec.w(nd - 2).data_ptr(), self.dec.b(nd - 2).data_ptr(),
+            self.dec.w(nd - 1).data_ptr(), self.dec.b(nd - 1).data_ptr(), x.data_ptr(), self.dec.outs[-1].data_ptr(),
+            self.dec.gouts[-2].data_ptr(), self.tail_llk_part.data_ptr(), C.byref(npart), self.tail_slab.data_ptr(),
+            C.byref(rows), None, self.hp(H_INVB), C.byref(self.dec.descs[-2]), b.desc['Cout'], st)
+      elif self.tail_mode is not None:
         lib.odin_gaussian_tail_fwd_bwd(
             h.data_ptr(), self.dec.w(nd - 2).data_ptr(), self.dec.b(nd - 2).data_ptr(),
             self.dec.w(nd - 1).data_ptr(), self.dec.b(nd - 1).data_ptr(), x.data_ptr(),
