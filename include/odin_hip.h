@@ -269,6 +269,46 @@ int odin_latent_tril_bwd(const float* p, const float* eps, const float* z, const
 int odin_latent_tril_sample_logprob(const float* p, const float* eps, float* z, float* logq, float* logp, int n,
                                     int B, int D, void* stream);
 
+/* ---- latent posterior q(z|x) = RelaxedOneHotCategorical(tau, logits): the Concrete / Gumbel-softmax latent
+ * (latent_concrete.hip).  RelaxedOneHotCategoricalLayer (odin/bay/layers/discrete.py:286-343; RVconf(K, 'relaxedonehot',
+ * projection=True), odin/bay/distribution_alias.py:113-114) is ONE K-way variable; the prior is OneHotCategorical with
+ * equal logits (random_variable.py:141-146).  p [B, K] are the logits l (no activation), tau > 0 a constant.
+ *   g ~ Gumbel(0, 1);  u = (l + g) / tau;  y = u - logsumexp(u);  z = exp(y)  (on the simplex; the decoder's input)
+ *   log q(z) = lgamma(K) + (K - 1) log tau + sum_k log_softmax(l - tau y)_k - sum_k y_k
+ *            = lgamma(K) + (K - 1) log tau - sum_k g_k - K logsumexp(-g) - sum_k y_k   (the form evaluated)
+ *   log p(z) = -log K sum_k z_k
+ * All arithmetic stays in y -- log(z) is never taken: where z underflows to 0 (tau = 0.1) kl, logq and dp stay finite.
+ * KL as odin_latent_fwd's `analytic`: 0 = the single-sample log q(z) - log p(z) at the z written (helpers.py:267-276),
+ * 1 = the categorical KL of Jang et al., sum_k pi_k (log pi_k + log K) with pi = softmax(l) (a departure: TFP registers
+ * no KL between the two distributions).  free_bits (units: K) / capacity / fbmask act on the per-sample scalar exactly
+ * as in odin_latent_fwd.
+ * odin_rng_gumbel: out[e] = -log(-log U_e), U_e = ((bits >> 8) + 0.5) 2^-24 with `bits` component e & 3 of Philox counter
+ *   e >> 2 under (seed, step_dev[0]) -- odin_rng_normal's counter scheme; never 0 or 1, so every value is finite and lies
+ *   in [-2.86, 17.33].
+ * odin_latent_concrete_fwd: draw = 0 reads the noise g [B, K]; draw = 1 draws it in the kernel -- bit for bit the stream
+ *   odin_rng_gumbel writes for (seed, step_dev) -- and STORES it to g (VAEEngine._latent_fwd: the step needs no RNG
+ *   launch).  Writes z [B, K], kl [B], fbmask [B].
+ * odin_latent_concrete_bwd (VAEEngine._backward_enc), with w = klw[0] fbmask_b, G = dz + dz_extra (either may be NULL),
+ *   a_j = G_j - sum_k G_k z_k:
+ *     analytic 0: dl_j = (z_j a_j - w (1 - K z_j)) / tau
+ *     analytic 1: dl_j = z_j a_j / tau + w pi_j (log pi_j - sum_k pi_k log pi_k)
+ *   klw is a DEVICE scalar as in odin_latent_bwd (graph replays see the beta schedule).  The gradients need z alone: g is
+ *   the step's noise buffer and is not read (it may be NULL).  Every element of dp [B, K] is written exactly once, no
+ *   float atomics: bit-reproducible.
+ * odin_latent_concrete_sample_logprob (VariationalAutoencoder.marginal_log_prob): the companion of
+ *   odin_latent_tril_sample_logprob -- p [B, K], g / z [n, B, K], logq / logp [n, B] (the single-sample forms above).
+ * One wave per sample, lane k owns category k.  Limits (-2, nothing launched, no output touched): 2 <= K <= 64,
+ * 1 <= B (n B) <= 2^31 - 16, tau > 0, analytic in {0, 1}. */
+int odin_rng_gumbel(float* out, size_t n, uint64_t seed, const int32_t* step_dev, void* stream);
+int odin_latent_concrete_fwd(const float* p, float* g, float* z, float* kl, float* fbmask, int B, int K, float tau,
+                             int analytic, float free_bits, const float* capacity, int draw, uint64_t seed,
+                             const int32_t* step_dev, void* stream);
+int odin_latent_concrete_bwd(const float* p, const float* g, const float* z, const float* dz, const float* dz_extra,
+                             const float* fbmask, const float* klw, float* dp, int B, int K, float tau, int analytic,
+                             void* stream);
+int odin_latent_concrete_sample_logprob(const float* p, const float* g, float* z, float* logq, float* logp, int n,
+                                        int B, int K, float tau, void* stream);
+
 /* ---- the bottleneck as one launch per direction (latent_block.hip): DistributionDense(P -> 2D) ->
  * MVNDiag(loc, softplus(raw)) -> reparameterised sample + KL term -> the decoder's first Dense(D -> N0)
  * (dense_distribution.py DistributionDense; variational_autoencoder.py:515-542; helpers.py:236-286;

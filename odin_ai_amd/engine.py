@@ -522,7 +522,8 @@ class VAEEngine:
                pseudoinputs_std: float = 0.01, pseudoinputs=None,
                vq_codes: Optional[int] = None, vq_code_size: Optional[int] = None, vq_commitment: float = 0.25,
                vq_ema: bool = False, vq_ema_decay: float = 0.99, vq_epsilon: float = 1e-5, vq_state=None,
-               latent_cov: str = 'diag', chain_fwd: bool = True):
+               latent_cov: str = 'diag', chain_fwd: bool = True, latent_dist: str = 'normal',
+               temperature: float = 0.5):
     """The keyword-only arguments are the engine's launch-order / A-B options (tests and tools pass them; the engine
     reads no environment variable):
       act_words        activation range words for the two-plane consumers; False: unscaled planes
@@ -582,7 +583,14 @@ class VAEEngine:
     neck and the latent block are not planned -- `neck` is ignored; 1 <= zdim <= 64):
       latent_cov      'diag' | 'tril': q(z|x) = MultivariateNormalTriL(loc, L); the projection is hdim -> D + D (D + 1) / 2
                       (loc | the raw values FillScaleTriL lays out as L), `p` / `dp` have that width; latent_reg='mmd'
-                      stays available (it reads z only)"""
+                      stays available (it reads z only)
+    The relaxed one-hot (Concrete / Gumbel-softmax) posterior (latent_concrete.hip; excludes tc, every
+    latent_reg, vamprior_components, vq_codes, latent_cov='tril', reverse=False, data parallelism, shared range_words and
+    an explicit neck_bwd; the neck and the latent block are not planned -- `neck` is ignored; 2 <= zdim <= 64):
+      latent_dist     'normal' | 'relaxedonehot': q(z|x) = RelaxedOneHotCategorical(temperature, logits), ONE zdim-way
+                      variable; the projection is hdim -> zdim (the logits), `p` / `dp` have that width, `eps` holds the
+                      Gumbel noise (train_step's `eps` argument is that noise; None: drawn inside the forward kernel)
+      temperature     its constant temperature (> 0)"""
     self.lib = lib if lib is not None else _lib.load()
     self.device = torch.device(device)
     self.B, self.D = int(batch_size), int(zdim)
@@ -595,6 +603,9 @@ class VAEEngine:
     if latent_cov not in ('diag', 'tril'):
       raise ValueError(f"latent_cov={latent_cov!r}: expected 'diag' or 'tril'")
     self.latent_cov = latent_cov
+    if latent_dist not in ('normal', 'relaxedonehot'):
+      raise ValueError(f"latent_dist={latent_dist!r}: expected 'normal' or 'relaxedonehot'")
+    self.latent_dist, self.temperature = latent_dist, float(temperature)
     self.set_kl_form(analytic, reverse)
     self.free_bits = -1.0 if free_bits is None else float(free_bits)
     self.tc_mode, self.world_size, self.seed = tc, int(world_size), int(seed)
@@ -622,8 +633,12 @@ class VAEEngine:
       self.vq_decay, self.vq_eps = float(vq_ema_decay), float(vq_epsilon)
     if latent_cov == 'tril':
       self._check_tril(tc, latent_reg, vamprior_components, vq_codes, range_words, neck_bwd)
-    # width of the latent projection: (loc | raw scale) or (loc | the D (D + 1) / 2 raw entries of L)
+    if latent_dist == 'relaxedonehot':
+      self._check_concrete(tc, latent_reg, vamprior_components, vq_codes, range_words, neck_bwd)
+    # width of the latent projection: (loc | raw scale), (loc | the D (D + 1) / 2 raw entries of L) or the K logits
     self.pw = self.D + self.D * (self.D + 1) // 2 if latent_cov == 'tril' else 2 * self.D
+    if latent_dist == 'relaxedonehot':
+      self.pw = self.D
     f32 = dict(dtype=torch.float32, device=self.device)
     # ---- parameters ----
     self.layout = ParamLayout()
@@ -746,6 +761,11 @@ class VAEEngine:
       self._plan_chain_fwd(bool(chain_fwd))
       if latent_cov == 'tril':
         self._plan_tril(bool(act_words))
+      elif latent_dist == 'relaxedonehot':
+        # the unfused latent slot only: neither the latent block nor the neck is planned (`neck` is ignored)
+        self.lat_block = self._used_block = False
+        self.neck = self._used_neck = False
+        self._neck_bwd_opt = None
       else:
         self._plan_latent_block(f32)
         self._neck_bwd_opt = neck_bwd
@@ -1099,6 +1119,31 @@ class VAEEngine:
     if neck_bwd:
       raise NotImplementedError("latent_cov='tril' with neck_bwd: the fused neck holds the diagonal latent block")
 
+  # ---- relaxed one-hot posterior (latent_concrete.hip) -----------------------------------------------------
+  def _check_concrete(self, tc, latent_reg, vamprior_components, vq_codes, range_words, neck_bwd):
+    who = "latent_dist='relaxedonehot'"
+    if self.latent_cov == 'tril':
+      raise ValueError(f"{who} cannot be combined with latent_cov='tril' (there is no Gaussian scale)")
+    if not 2 <= self.D <= 64:
+      raise ValueError(f'{who}: zdim={self.D} outside the kernel (2 .. 64: a category per lane)')
+    if not self.temperature > 0.0:
+      raise ValueError(f'{who}: temperature={self.temperature} must be positive')
+    if tc is not None:
+      raise ValueError(f'{who} cannot be combined with tc={tc!r} (the estimator reads a Gaussian posterior)')
+    if latent_reg is not None:
+      raise ValueError(f'{who} cannot be combined with latent_reg={latent_reg!r} (the regularisers compare against a '
+                       f'Gaussian prior sample or read a Gaussian scale)')
+    if vamprior_components is not None:
+      raise ValueError(f"{who} cannot be combined with vamprior_components (the mixture's components are Gaussian)")
+    if vq_codes is not None:
+      raise ValueError(f'{who} cannot be combined with vq_codes (the quantiser has no posterior distribution)')
+    if self.is_dp:
+      raise NotImplementedError(f'{who} under data parallelism (world_size > 1 / force_dp) is not offered')
+    if range_words is not None:
+      raise NotImplementedError(f'{who} on shared range_words is not offered')
+    if neck_bwd:
+      raise NotImplementedError(f'{who} with neck_bwd: the fused neck holds the Gaussian latent block')
+
   def _plan_tril(self, act_words: bool):
     """the unfused latent slot only (`neck` / the latent block are not planned); the two range words of the projection
     where its launches read planes (both widths >= 256 and multiples of 8, a batch of at least 32: D = 29, 32, 45, ...,
@@ -1218,6 +1263,9 @@ class VAEEngine:
                       'cached sample from the prior, which has none')
     if not reverse and self.latent_cov == 'tril':
       raise NotImplementedError("latent_cov='tril' with reverse=False: KL(p || q) needs the inverse of L")
+    if not reverse and self.latent_dist == 'relaxedonehot':
+      raise NotImplementedError("latent_dist='relaxedonehot' with reverse=False: KL(p || q) of a one-hot prior against "
+                                'a density on the simplex is not defined')
     self.analytic = 2 if not reverse else int(bool(analytic))
 
   def n_params_end(self) -> int:
@@ -1670,6 +1718,14 @@ class VAEEngine:
                                 self.dec.b(0).data_ptr(), self.dec.outs[0].data_ptr(), B, self.hdim, D,
                                 r0.N, ACT[r0.act], int(self.analytic), self.free_bits, cap, st)
       return self.dec.outs[0], 1
+    if self.latent_dist == 'relaxedonehot':
+      # (the Gumbel noise is drawn inside the latent kernel, which leaves it in self.eps: no RNG launch)
+      h_e = self.enc.forward(x, st)
+      lib.odin_dense_fwd(h_e.data_ptr(), lw.data_ptr(), lb.data_ptr(), self.p.data_ptr(), B, self.hdim, self.pw, 0, st)
+      lib.odin_latent_concrete_fwd(self.p.data_ptr(), self.eps.data_ptr(), self.z.data_ptr(), self.kl.data_ptr(),
+                                   self.fbmask.data_ptr(), B, D, self.temperature, int(self.analytic), self.free_bits,
+                                   cap, int(eps is None), self.seed, self.hp(N_HYPER), st)
+      return self.z, 0
     if eps is None:
       lib.odin_rng_normal(self.eps.data_ptr(), B * D, self.seed, self.hp(N_HYPER), st)
     h_e = self.enc.forward(x, st)
@@ -2042,12 +2098,17 @@ class VAEEngine:
       if bslab is not None:
         jobs.append(self._slab_job(bslab, last.b_off, rows.value))
     else:
-      lib.odin_latent_bwd(self.p.data_ptr(), self.eps.data_ptr(), self.z.data_ptr(),
-                          self.dz.data_ptr(), dzx, self.fbmask.data_ptr(), self.hp(H_KLW), tl, ts,
-                          self.dp.data_ptr(), B, D, int(self.analytic), st)
+      if self.latent_dist == 'relaxedonehot':
+        lib.odin_latent_concrete_bwd(self.p.data_ptr(), self.eps.data_ptr(), self.z.data_ptr(), self.dz.data_ptr(), dzx,
+                                     self.fbmask.data_ptr(), self.hp(H_KLW), self.dp.data_ptr(), B, D, self.temperature,
+                                     int(self.analytic), st)
+      else:
+        lib.odin_latent_bwd(self.p.data_ptr(), self.eps.data_ptr(), self.z.data_ptr(),
+                            self.dz.data_ptr(), dzx, self.fbmask.data_ptr(), self.hp(H_KLW), tl, ts,
+                            self.dp.data_ptr(), B, D, int(self.analytic), st)
       rows = C.c_int(0)
       lib.odin_dense_wgrad(h_e.data_ptr(), self.dp.data_ptr(), self.lat_slab.data_ptr(),
-                           C.byref(rows), B, self.hdim, 2 * D,
+                           C.byref(rows), B, self.hdim, self.pw,
                            st if (fork is None or not fork.wants(True)) else fork(-1))  # small
       jobs.append(self._slab_job(self.lat_slab, self.lat_w_off, rows.value))
       auxp = h_e.data_ptr() if aux_act != 0 else None
@@ -2056,7 +2117,7 @@ class VAEEngine:
       top = self.enc.set_top_word(True)
       lib.odin_dense_bwd(None, self.dp.data_ptr(), lw.data_ptr(), auxp, aux_act, self.enc.gouts[-1].data_ptr(),
                          bslab.data_ptr() if bslab is not None else None, C.byref(rows), None, None, B,
-                         self.hdim, 2 * D, 0, 1, None, top, st)
+                         self.hdim, self.pw, 0, 1, None, top, st)
       if bslab is not None:
         jobs.append(self._slab_job(bslab, last.b_off, rows.value))
     if not self._bwd_neck():

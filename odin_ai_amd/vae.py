@@ -10,6 +10,8 @@ arguments, method names, returned structures and error behaviour):
   odin/bay/vi/autoencoder/info_vae.py:28-91               (InfoVAE: maximum-mean discrepancy)
   odin/bay/vi/autoencoder/dip_vae.py                      (DIPVAE: disentangled inferred prior)
   odin/networks/base_networks.py:415-812                  (optimize(), fit())
+  odin/bay/layers/continuous.py:459-483                   (latent posteriors 'mvndiag' and 'mvntril')
+  odin/bay/layers/discrete.py:286-343                     (latent posterior 'relaxedonehot' / 'relaxedsoftmax')
 
 Tensors are torch tensors on the model's device; returned "distributions" are light
 objects exposing what callers of the reference use (mean / stddev / sample / log_prob /
@@ -55,6 +57,8 @@ class KLdivergence:
                       '"posterior" is the prior, which carries no cached sample)')
     if isinstance(q, MVNTriLPosterior):
       return self._tril(q, analytic, reverse, free_bits, keepdims)
+    if isinstance(q, RelaxedOneHotPosterior):
+      return self._concrete(q, analytic, reverse, free_bits, keepdims)
     if not reverse:  # KL(p || q), helpers.py:261-265
       kl = (torch.log(q.scale) + 0.5 * (1.0 + q.loc ** 2) / q.scale ** 2 - 0.5).sum(-1)
     elif analytic:
@@ -84,6 +88,25 @@ class KLdivergence:
       kl = q.log_prob(q.z) - (-0.5 * (q.z ** 2).sum(-1) - 0.5 * D * LOG2PI)
     if free_bits is not None:
       kl = torch.clamp(kl, min=free_bits * D)
+    if analytic and keepdims:
+      kl = kl.unsqueeze(0)
+    return kl
+
+
+  @staticmethod
+  def _concrete(q: 'RelaxedOneHotPosterior', analytic, reverse, free_bits, keepdims):
+    if not reverse:
+      raise NotImplementedError(CONCRETE_NO_FORWARD_KL)
+    K = q.logits.shape[-1]
+    if analytic:
+      # (TFP registers no KL between RelaxedOneHotCategorical and OneHotCategorical: the categorical KL of Jang et al.
+      # against the uniform prior -- DESIGN 3.16)
+      lp = torch.log_softmax(q.logits, -1)
+      kl = (lp.exp() * (lp + math.log(K))).sum(-1)
+    else:
+      kl = q.log_prob_cached() + math.log(K) * q.z.sum(-1)
+    if free_bits is not None:
+      kl = torch.clamp(kl, min=free_bits * K)
     if analytic and keepdims:
       kl = kl.unsqueeze(0)
     return kl
@@ -179,6 +202,65 @@ class MVNTriLPosterior:
     e = torch.linalg.solve_triangular(L, d, upper=False).squeeze(-1)   # (host-side solve: L e = z - loc)
     return -0.5 * (e ** 2).sum(-1) - torch.log(torch.diagonal(self.scale_tril, dim1=-2, dim2=-1)).sum(-1) \
         - 0.5 * D * LOG2PI
+
+  def __array__(self):
+    return self.z.detach().cpu().numpy()
+
+  def tensor(self):
+    """tf.convert_to_tensor(q): the cached sample."""
+    return self.z
+
+
+CONCRETE_NO_FORWARD_KL = ("'relaxedonehot' with reverse=False: KL(p || q) of a one-hot prior against a density on the "
+                          'simplex is not defined')
+
+
+class RelaxedOneHotPosterior:
+  """RelaxedOneHotCategorical(temperature, logits) with its cached sample (odin/bay/layers/discrete.py:286-343): ONE
+  K-way variable.  p [B, K] are the logits, g [B, K] the Gumbel noise the cached sample z = softmax((logits + g) / tau)
+  was drawn with -- kept so that the cached sample's density is evaluated in y = log z without taking log(z), which
+  underflows at low temperatures."""
+
+  def __init__(self, p: torch.Tensor, z: torch.Tensor, g: torch.Tensor, temperature: float):
+    self.logits = p
+    self.temperature = float(temperature)
+    self.z, self.noise = z, g
+    self.KL_divergence = KLdivergence(self, prior='OneHotCategorical(logits=0)')
+
+  event_shape = property(lambda self: (self.logits.shape[-1],))
+  batch_shape = property(lambda self: tuple(self.logits.shape[:-1]))
+
+  @property
+  def probs(self):
+    return torch.softmax(self.logits, -1)
+
+  def mean(self):
+    raise NotImplementedError('RelaxedOneHotCategorical has no closed-form mean (TFP raises too)')
+
+  def _gumbel(self, shp, seed=None):
+    g = None
+    if seed is not None:
+      g = torch.Generator(device=self.logits.device).manual_seed(int(seed))
+    u = torch.rand(shp, device=self.logits.device, generator=g).clamp_(2.0 ** -25, 1.0 - 2.0 ** -24)
+    return -torch.log(-torch.log(u))
+
+  def sample(self, n=None, seed=None):
+    shp = tuple(self.logits.shape) if n is None else (int(n),) + tuple(self.logits.shape)
+    return torch.softmax((self.logits + self._gumbel(shp, seed)) / self.temperature, -1)
+
+  def _log_prob_y(self, y):
+    K, tau = self.logits.shape[-1], self.temperature
+    return (math.lgamma(K) + (K - 1) * math.log(tau)
+            + torch.log_softmax(self.logits - tau * y, -1).sum(-1) - y.sum(-1))
+
+  def log_prob(self, z):
+    """the density on the simplex at any z (its logarithm is taken: entries that underflowed to 0 are held at the
+    smallest normal float)"""
+    return self._log_prob_y(torch.log(torch.clamp(z, min=torch.finfo(z.dtype).tiny)))
+
+  def log_prob_cached(self):
+    """log q(z) at the cached sample, from its noise: y = log_softmax((logits + g) / tau)"""
+    return self._log_prob_y(torch.log_softmax((self.logits + self.noise) / self.temperature, -1))
 
   def __array__(self):
     return self.z.detach().cpu().numpy()
@@ -409,10 +491,22 @@ class VariationalAutoencoder:
       if not isinstance(net, SequentialNetwork):
         raise ValueError(f'{n} must be a SequentialNetwork description, got {type(net)}')
     posterior = latents.posterior
-    if posterior not in ('mvndiag', 'diag', 'normaldiag', 'mvntril', 'tril'):
+    if posterior not in ('mvndiag', 'diag', 'normaldiag', 'mvntril', 'tril', 'relaxedonehot', 'relaxedsoftmax'):
       raise ValueError(f"latents posterior {latents.posterior!r} is outside the HIP path "
-                       f"(supported: 'mvndiag', 'mvntril')")
+                       f"(supported: 'mvndiag', 'mvntril', 'relaxedonehot')")
     self._latent_cov = 'tril' if posterior in ('mvntril', 'tril') else 'diag'
+    self._latent_dist = 'relaxedonehot' if posterior in ('relaxedonehot', 'relaxedsoftmax') else 'normal'
+    # (RelaxedOneHotCategoricalLayer's default temperature, discrete.py:286-343)
+    self._temperature = float(latents.kwargs.get('temperature', 0.5))
+    if self._latent_dist == 'relaxedonehot':
+      if self._concrete_refusal is not None:
+        raise ValueError(f"{type(self).__name__} with a 'relaxedonehot' posterior: {self._concrete_refusal}")
+      if len(tuple(latents.event_shape)) != 1:
+        raise ValueError(f"'relaxedonehot': event_shape={latents.event_shape} must be one K-way variable")
+      if not self._temperature > 0.0:
+        raise ValueError(f"'relaxedonehot': temperature={self._temperature} must be positive")
+      if not reverse:
+        raise NotImplementedError(CONCRETE_NO_FORWARD_KL)
     if self._latent_cov == 'tril':
       if self._tril_refusal is not None:
         raise ValueError(f"{type(self).__name__} with a 'mvntril' posterior: {self._tril_refusal}")
@@ -469,6 +563,7 @@ class VariationalAutoencoder:
                       lib=self._lib, params=self._params, seed=self.seed + self._rank(),
                       optim_state=self._optim_state, world_size=self._world_size(),
                       force_dp=bool(getattr(self, 'force_dp', False)), latent_cov=self._latent_cov,
+                      **self._latent_dist_options(),
                       **self._reg_options(), **getattr(self, 'engine_options', {}))
       if self._params is None:
         self._params = eng.params
@@ -480,6 +575,13 @@ class VariationalAutoencoder:
         broadcast_parameters(eng.params, src=0)
       self._engines[B] = eng
     return self._engines[B]
+
+  def _latent_dist_options(self) -> dict:
+    """the engine keywords of a non-Gaussian posterior (none for the Gaussian ones: their engines are built with the
+    arguments they always were)"""
+    if self._latent_dist == 'normal':
+      return {}
+    return dict(latent_dist=self._latent_dist, temperature=self._temperature)
 
   def _world_size(self) -> int:
     import torch.distributed as dist
@@ -533,6 +635,8 @@ class VariationalAutoencoder:
     """odin/bay/vi/_base.py:51-89"""
     if reverse is not None and not reverse and self._latent_cov == 'tril':
       raise NotImplementedError("'mvntril' with reverse=False: KL(p || q) needs the inverse of L")
+    if reverse is not None and not reverse and self._latent_dist == 'relaxedonehot':
+      raise NotImplementedError(CONCRETE_NO_FORWARD_KL)
     if analytic is not None:
       self.analytic = bool(analytic)
     if reverse is not None:
@@ -585,9 +689,13 @@ class VariationalAutoencoder:
 
   # why a model class cannot take the full-covariance posterior ('mvntril'); None: it can
   _tril_refusal: Optional[str] = None
+  # the same for the relaxed one-hot posterior ('relaxedonehot')
+  _concrete_refusal: Optional[str] = None
 
   # ------------------------------------------------------------------ forward API
-  def _posterior(self, eng: VAEEngine) -> Union[MVNDiagPosterior, MVNTriLPosterior]:
+  def _posterior(self, eng: VAEEngine) -> Union[MVNDiagPosterior, MVNTriLPosterior, RelaxedOneHotPosterior]:
+    if self._latent_dist == 'relaxedonehot':
+      return RelaxedOneHotPosterior(eng.p.clone(), eng.z.clone(), eng.eps.clone(), self._temperature)
     cls = MVNTriLPosterior if self._latent_cov == 'tril' else MVNDiagPosterior
     return cls(eng.p.clone(), eng.z.clone(), eng.D)
 
@@ -613,7 +721,8 @@ class VariationalAutoencoder:
 
   def decode(self, latents, training=None, mask=None, only_decoding=False, **kwargs):
     """variational_autoencoder.py:316-360"""
-    z = latents.tensor() if isinstance(latents, (MVNDiagPosterior, MVNTriLPosterior)) else latents
+    z = latents.tensor() if isinstance(latents, (MVNDiagPosterior, MVNTriLPosterior, RelaxedOneHotPosterior)) \
+        else latents
     z = _as_tensor(z, self.device)
     eng = self._engine(z.shape[0])
     h = eng.run_decoder(z).clone()
@@ -666,6 +775,9 @@ class VariationalAutoencoder:
 
   def sample_prior(self, n: int = 1, seed: int = 1) -> torch.Tensor:
     g = torch.Generator(device='cpu').manual_seed(int(seed))
+    if self._latent_dist == 'relaxedonehot':   # OneHotCategorical with equal logits: one-hot rows
+      idx = torch.randint(self.zdim, (int(n),), generator=g)
+      return torch.nn.functional.one_hot(idx, self.zdim).to(dtype=torch.float32, device=self.device)
     return torch.randn(int(n), self.zdim, generator=g).to(self.device)
 
   def sample_observation(self, n: int = 1, seed: int = 1, training=False, **kwargs):
@@ -692,16 +804,22 @@ class VariationalAutoencoder:
       lib, st = eng.lib, eng.stream()
       eng.set_hyper(beta=1.0, t=self._step, **self._hyper_extra())
       eng.run_encoder(x)  # fills eng.p = (loc | raw scale)
+      concrete = self._latent_dist == 'relaxedonehot'
       if eps is None:
         e = torch.empty(n, B, D, **f32)
-        lib.odin_rng_normal(e.data_ptr(), n * B * D, self.seed + 7919 + i0, eng.hp(N_HYPER), st)
+        rng = lib.odin_rng_gumbel if concrete else lib.odin_rng_normal
+        rng(e.data_ptr(), n * B * D, self.seed + 7919 + i0, eng.hp(N_HYPER), st)
       else:
         e = _as_tensor(eps, self.device)[:, i0:i0 + B].contiguous()
       z = torch.empty(n, B, D, **f32)
       lq, lp, llk = torch.empty(n, B, **f32), torch.empty(n, B, **f32), torch.empty(n, B, **f32)
-      sample_logprob = (lib.odin_latent_tril_sample_logprob if self._latent_cov == 'tril'
-                        else lib.odin_latent_sample_logprob)
-      sample_logprob(eng.p.data_ptr(), e.data_ptr(), z.data_ptr(), lq.data_ptr(), lp.data_ptr(), n, B, D, st)
+      if concrete:
+        lib.odin_latent_concrete_sample_logprob(eng.p.data_ptr(), e.data_ptr(), z.data_ptr(), lq.data_ptr(),
+                                                lp.data_ptr(), n, B, D, self._temperature, st)
+      else:
+        sample_logprob = (lib.odin_latent_tril_sample_logprob if self._latent_cov == 'tril'
+                          else lib.odin_latent_sample_logprob)
+        sample_logprob(eng.p.data_ptr(), e.data_ptr(), z.data_ptr(), lq.data_ptr(), lp.data_ptr(), n, B, D, st)
       self._prior_log_prob(eng, z, lp)
       # decode the n*B codes in chunks of whole sample-rows (bounded activation memory)
       rows = max(1, min(n, 2048 // max(B, 1)))
@@ -1112,6 +1230,7 @@ class BetaTCVAE(BetaVAE):
   the KL is ALSO scaled by beta through BetaVAE.elbo_components (:42)."""
 
   _tril_refusal = 'the total-correlation estimator reads a diagonal scale'
+  _concrete_refusal = 'the total-correlation estimator reads a Gaussian posterior'
 
   def __init__(self, beta: float = 1.0, name='BetaTCVAE', **kwargs):
     super().__init__(beta=beta, name=name, **kwargs)
@@ -1149,6 +1268,7 @@ class InfoVAE(BetaVAE):
     self.beta = 1.0 - float(alpha)
 
   _reg_key = 'div'
+  _concrete_refusal = "the MMD's prior sample is Gaussian"
 
   def _reg_options(self) -> dict:
     return dict(latent_reg='mmd', reg_coef=self.lamda - self.beta, mmd_kernel=self.mmd_kernel,
@@ -1171,6 +1291,7 @@ class DIPVAE(BetaVAE):
 
   _reg_key = 'dip'
   _tril_refusal = 'the disentangled-inferred-prior penalty reads a diagonal scale'
+  _concrete_refusal = 'the disentangled-inferred-prior penalty reads a Gaussian mean and scale'
 
   def _reg_options(self) -> dict:
     return dict(latent_reg='dip_i' if self.only_mean else 'dip_ii', reg_coef=1.0,
@@ -1247,6 +1368,7 @@ class VampriorVAE(BetaVAE):
   analytic / forward KL, free_bits, sample_shape other than (), data parallelism."""
 
   _tril_refusal = "the mixture's components read a diagonal scale"
+  _concrete_refusal = "the mixture's components are Gaussian"
 
   def __init__(self, n_components: int = 500, pseudoinputs_mean: float = -0.05, pseudoinputs_std: float = 0.01,
                beta: Union[float, Interpolation] = linear(vmin=1e-6, vmax=1., steps=2000, delay_in=0),
@@ -1416,6 +1538,7 @@ class VQVAE(BetaVAE):
   free_bits, sample_shape other than (), marginal_log_prob (the posterior has no density), data parallelism."""
 
   _tril_refusal = 'the quantised latent has no Gaussian posterior'
+  _concrete_refusal = 'the quantised latent has no posterior distribution'
 
   def __init__(self, n_codes: int = 64, commitment_weight: float = 0.25, distance_metric: str = 'euclidean',
                trainable_prior: bool = False, ema_decay: float = 0.99, ema_update: bool = False,
@@ -1656,6 +1779,7 @@ class FactorVAE(AnnealingVAE):
   when `use_graph` / `fit(compile_graph=True)`."""
 
   _tril_refusal = 'its forward-only second engine shares range words, which the triangular path does not offer'
+  _concrete_refusal = 'its forward-only second engine shares range words, which the relaxed one-hot path does not offer'
 
   def __init__(self, discriminator_units: Sequence[int] = (1000,) * 5, discriminator_optim=None,
                activation: str = 'relu', batchnorm: bool = False, tc_coef: float = 7.0,
