@@ -426,6 +426,20 @@ int odin_elbo_bernoulli_fwd_bwd(const float* logits, const float* x, float* llk_
 int odin_elbo_bernoulli_fwd_bwd_ranged(const float* logits, const float* x, float* llk_part,
                                        float* dlogits, const float* scale, int B, int n_per_sample,
                                        int* n_part_out, uint32_t* dlogits_amax, void* stream);
+/* Independent(ContinuousBernoulli(logits),3).log_prob(x) ('cbernoulli', odin/bay/distribution_alias.py:108;
+ * ContinuousBernoulliLayer, odin/bay/layers/discrete.py:82-121; elbo_cbernoulli.hip) for targets x in [0, 1], in logit
+ * space: log p = x l - A(l), A(l) = log((e^l - 1) / l), A(0) = 0; dlogits = -(x - mu(l)) * scale[0] with mu = A' the
+ * distribution's mean, so |dlogits| <= scale[0].  The five-term series below |l| = 1, the closed forms above (one exp,
+ * one log, one reciprocal per element); the reference's `lims` band around probs = 1/2 has no counterpart here.
+ * Contract of odin_elbo_bernoulli_fwd_bwd_ranged: llk_part[b][part], a NULL logits pointer is a dry run that reports
+ * n_part, dlogits_amax (optional) receives max |dlogits|, fixed-order reductions (equal bits on every launch).
+ * n_part depends on the shape alone: n_per_sample / 256 where n_per_sample % 256 == 0 and B * n_per_sample >= 2^20 --
+ * served by a persistent grid-stride kernel when the three pointers are 16-byte aligned -- and ceil(n_per_sample / 1024)
+ * otherwise (16-byte accesses where n_per_sample % 4 == 0 and the pointers are aligned, scalar ones otherwise).
+ * -2, nothing launched, no output touched: B < 1, n_per_sample < 1 or > 2^30, more than 2^31 - 1 partials. */
+int odin_elbo_cbernoulli_fwd_bwd(const float* logits, const float* x, float* llk_part, float* dlogits,
+                                 const float* scale, int B, int n_per_sample, int* n_part_out,
+                                 uint32_t* dlogits_amax, void* stream);
 /* Independent(Normal(loc, scale)) with params = split(h,2,axis=-1)
  * (image_networks.py:95-102): softplus1 = 1 -> scale = softplus(raw + softplus^-1(1))
  * (GaussianLayer, odin/bay/layers/continuous.py:196-260; odin/backend/maths.py:279-281);
@@ -449,7 +463,9 @@ int odin_elbo_gaussian_fwd_bwd(const float* h, const float* x, float* llk_part, 
  * C in {1, 3}; a NULL h is a dry run that reports n_part / rows; -2: shapes outside the kernel.
  * softplus1 = 3: the Bernoulli observation instead (image_networks.py:87-93): w1 [Cin, C], logits [B, n_pix, C],
  * llk = Independent(Bernoulli(logits)).log_prob(target) -- a Bernoulli decoder whose last two layers do not fit
- * odin_bernoulli_tail_fwd_bwd's plane kernel (5x5 kernels, rows that are not 8 / 16 / 32 pixels wide). */
+ * odin_bernoulli_tail_fwd_bwd's plane kernel (5x5 kernels, rows that are not 8 / 16 / 32 pixels wide).
+ * softplus1 = 4: the continuous Bernoulli (odin_elbo_cbernoulli_fwd_bwd's log-prob and gradient) over the same C maps:
+ * mode 3 with another element function, every 'cbernoulli' decoder that ends in a 1x1 head. */
 /* Between _begin and _end the calling thread's weight gradients of the 4x4 / stride-2 plane layers are collected
  * instead of launched, and _end issues them as ONE multi-layer launch on the stream they were given (they depend on
  * nothing but their own layer's tensors; a backward pass has five of them: -4 launches).  odin_slab_reduce issues

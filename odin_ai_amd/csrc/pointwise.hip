@@ -8,6 +8,7 @@
 #include "odin_device.h"
 #include "odin_internal.h"
 #include "odin_latent_math.h"
+#include "odin_cbern.h"
 #include <cstdlib>
 #include <cstdint>
 
@@ -1055,7 +1056,8 @@ extern "C" int odin_elbo_bernoulli_fwd_bwd_ranged(const float* logits, const flo
 constexpr int GH_NT = 512;   // threads per workgroup
 constexpr int GH_U = 4;      // pixel groups in flight per lane (8: 116 -> 187 us, register pressure)
 // SP1 = 0 / 1: Normal(loc, raw | softplus1(raw)) over 2C maps; SP1 = 3: Bernoulli(logits) over C maps
-// (image_networks.py:87-93)
+// (image_networks.py:87-93); SP1 = 4: ContinuousBernoulli(logits) over C maps (odin/bay/layers/discrete.py:82-121) --
+// mode 3 with the element's log-prob and its derivative from cbern1 (odin_cbern.h)
 template <int C, int SP1>
 __global__ __launch_bounds__(GH_NT) void gauss_head_kernel(
     const float4* __restrict__ h, const float* __restrict__ w1, const float* __restrict__ b1,
@@ -1063,7 +1065,8 @@ __global__ __launch_bounds__(GH_NT) void gauss_head_kernel(
     float4* __restrict__ dh, float* __restrict__ llk_part, float* __restrict__ wslab, float* __restrict__ colsum,
     const float* __restrict__ scale, unsigned* dh_amax, int n_units, int n_part, int n_pix, int Q, int h_act,
     int upw) {
-  constexpr int CO = SP1 == 3 ? C : 2 * C, NWV = GH_NT / 64;
+  constexpr bool ONE = SP1 == 3 || SP1 == 4;   // one parameter map per channel
+  constexpr int CO = ONE ? C : 2 * C, NWV = GH_NT / 64;
   __shared__ float wl[64 * CO];
   __shared__ float red[NWV * 8 * (5 * CO + 4) + 16];
   const int CI = 4 * Q;
@@ -1159,7 +1162,11 @@ __global__ __launch_bounds__(GH_NT) void gauss_head_kernel(
           bern1(lg[c], t[u][c], sc, l1, dl[c]);
           continue;
         }
-        const float loc = lg[c], raw = lg[SP1 == 3 ? c : C + c];
+        if constexpr (SP1 == 4) {
+          cbern1(lg[c], t[u][c], sc, l1, dl[c]);
+          continue;
+        }
+        const float loc = lg[c], raw = lg[ONE ? c : C + c];
         float sd, dsd;
         if (SP1 == 1) {  // softplus1(raw) = softplus(raw + softplus^-1(1)); its derivative = sigmoid(same)
           const float a = raw + SOFTPLUS_INV1;
@@ -1175,7 +1182,7 @@ __global__ __launch_bounds__(GH_NT) void gauss_head_kernel(
         const float d = (t[u][c] - loc) * inv;
         l1 += -0.5f * d * d - 0.6931471805599453f * odin_log2(sd) - 0.5f * LOG2PI_F;
         dl[c] = -(d * inv) * sc;
-        dl[SP1 == 3 ? c : C + c] = -((d * d - 1.f) * inv) * dsd * sc;
+        dl[ONE ? c : C + c] = -((d * d - 1.f) * inv) * dsd * sc;
       }
       if (!ok) {
 #pragma unroll
@@ -1268,7 +1275,8 @@ __global__ __launch_bounds__(GH_NT) void gauss_head_kernel(
 }
 
 // h [B * n_pix, Cin] = the decoder's activation below the 1x1 head (act h_act already applied), w1 [Cin, 2C], b1 [2C],
-// target [B, n_pix, C].  Writes logits [B, n_pix, 2C], dlogits (optional) = -scale * d llk / d logits, dh [B * n_pix,
+// target [B, n_pix, C]; softplus1 = 3 / 4: the Bernoulli / continuous Bernoulli over C maps (w1 [Cin, C], b1 [C],
+// logits [B, n_pix, C]).  Writes logits [B, n_pix, 2C], dlogits (optional) = -scale * d llk / d logits, dh [B * n_pix,
 // Cin], llk_part [B][n_part], one row (dW1 | db1) per workgroup of wslab and (optional) one row of Cin column sums of
 // dh per workgroup of colsum_slab.  NULL h: dry run that reports n_part / rows.  -2: shapes outside this kernel.
 extern "C" int odin_gaussian_head_fwd_bwd(const float* h, const float* w1, const float* b1, const float* target,
@@ -1277,7 +1285,7 @@ extern "C" int odin_gaussian_head_fwd_bwd(const float* h, const float* w1, const
                                           const float* scale, int B, int n_pix, int Cin, int C, int softplus1,
                                           int h_act, uint32_t* dh_amax, void* stream) {
   if (!(Cin == 8 || Cin == 16 || Cin == 32) || (C != 1 && C != 3) ||
-      (softplus1 != 0 && softplus1 != 1 && softplus1 != 3) || B < 1 ||
+      (softplus1 != 0 && softplus1 != 1 && softplus1 != 3 && softplus1 != 4) || B < 1 ||
       n_pix < 1 || (size_t)B * n_pix * Cin * 4 >= (1ull << 40))
     return odin_fail(-2, "gaussian_head: shapes outside the fused kernel");
   const int Q = Cin / 4;
@@ -1306,6 +1314,7 @@ extern "C" int odin_gaussian_head_fwd_bwd(const float* h, const float* w1, const
               logits, dlogits, (float4*)dh, llk_part, wslab, colsum_slab, scale, (unsigned*)dh_amax,             \
               (int)n_units, n_part, n_pix, Q, h_act, upw)
   if (softplus1 == 3) { if (C == 1) ODIN_GH(1, 3); else ODIN_GH(3, 3); }
+  else if (softplus1 == 4) { if (C == 1) ODIN_GH(1, 4); else ODIN_GH(3, 4); }
   else if (C == 1 && softplus1 == 1) ODIN_GH(1, 1);
   else if (C == 1) ODIN_GH(1, 0);
   else if (softplus1 == 1) ODIN_GH(3, 1);

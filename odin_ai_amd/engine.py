@@ -473,7 +473,7 @@ MIXQL_K = 10  # components of the 'mixqlogistic' observation (image_networks.py:
 
 def observation_maps(observation: str, C: int) -> int:
   """parameter maps the decoder emits per pixel for an observation over C channels."""
-  if observation == 'bernoulli':
+  if observation in ('bernoulli', 'cbernoulli'):
     return C
   if observation == 'mixqlogistic':
     return MIXQL_K * (2 * C + C * (C - 1) // 2 + 1)
@@ -501,7 +501,7 @@ class LatentTerm(NamedTuple):
 class VAEEngine:
   """encoder -> q(z|x) -> decoder -> ELBO -> backward -> Adam for a FIXED batch size.
 
-  observation: 'bernoulli' | 'gaussian' | 'gaussian_softplus1' | 'qlogistic' | 'mixqlogistic'
+  observation: 'bernoulli' | 'cbernoulli' | 'gaussian' | 'gaussian_softplus1' | 'qlogistic' | 'mixqlogistic'
   tc: None | 'betatc' (total_correlation, weight (beta-1))
   latent_reg: None | 'mmd' | 'dip_i' | 'dip_ii' (InfoVAE's maximum-mean discrepancy / DIPVAE's penalty, weight reg_coef)
   """
@@ -712,7 +712,8 @@ class VAEEngine:
     # tensor: no absmax pass per step for it (the dense MNIST step: 5 of 125 us).  (Round 6 handed the consumers the
     # a-priori bound 1 / B as a static word instead; that bound holds only for targets in [0, 1], and the reference's
     # Bernoulli takes any real target: a target of 6 overflowed the planes to inf.)
-    self._bern_keeps_top = observation == 'bernoulli' and bool(static_top_word)
+    # (the continuous Bernoulli's kernel does the same: dlogits = (mu(l) - x) / B_global)
+    self._bern_keeps_top = observation in ('bernoulli', 'cbernoulli') and bool(static_top_word)
     if self._bern_keeps_top:
       self.dec.set_top_word(True)
     self.p = torch.empty(B, self.pw, **f32)
@@ -1357,11 +1358,12 @@ class VAEEngine:
     the activation below the head instead of three."""
     self.gauss_head = self._used_head = False
     recs = self.dec_recs
-    if self.observation not in ('gaussian', 'gaussian_softplus1', 'bernoulli') or len(recs) < 2:
+    if self.observation not in ('gaussian', 'gaussian_softplus1', 'bernoulli', 'cbernoulli') or len(recs) < 2:
       return
     a, b = recs[-2], recs[-1]
     Cc = self.in_shape[-1]
-    bern = self.observation == 'bernoulli'
+    # ('cbernoulli': the Bernoulli's C maps and shape conditions; no fused tail is ever planned for it)
+    bern = self.observation in ('bernoulli', 'cbernoulli')
     if not (b.kind == 'conv' and b.desc['K'] == 1 and b.desc['stride'] == 1 and b.act == 'linear'
             and b.desc['Cout'] == (Cc if bern else 2 * Cc) and a.kind in ('conv', 'deconv')):
       return
@@ -1375,8 +1377,9 @@ class VAEEngine:
       mac = self.B * (d['OH'] * d['OW'] if a.kind == 'conv' else d['H'] * d['W']) * d['K'] ** 2 * d['Cin'] * d['Cout']
       if self.tail_keeps_range or 2.0 * mac < 1.2e9:
         return
-    # (mode of odin_gaussian_head_fwd_bwd: 0 / 1 = Normal with a raw / softplus1 scale, 3 = Bernoulli)
-    self.head_mode = 3 if bern else OBS_MODE[self.observation]
+    # (mode of odin_gaussian_head_fwd_bwd: 0 / 1 = Normal with a raw / softplus1 scale, 3 = Bernoulli, 4 = continuous
+    # Bernoulli)
+    self.head_mode = (4 if self.observation == 'cbernoulli' else 3) if bern else OBS_MODE[self.observation]
     rows, npart = C.c_int(0), C.c_int(0)
     try:
       self.lib.odin_gaussian_head_fwd_bwd(None, None, None, None, None, None, None, None, C.byref(npart), None,
@@ -1772,6 +1775,8 @@ class VAEEngine:
     npart = C.c_int(0)
     if self.observation == 'bernoulli':
       lib.odin_elbo_bernoulli_fwd_bwd_ranged(h_d, x, part, dlogits, inv_b, B, self.n_per, C.byref(npart), top_word, st)
+    elif self.observation == 'cbernoulli':
+      lib.odin_elbo_cbernoulli_fwd_bwd(h_d, x, part, dlogits, inv_b, B, self.n_per, C.byref(npart), top_word, st)
     elif self.observation == 'mixqlogistic':
       lib.odin_elbo_mixqlogistic_fwd_bwd(h_d, x, part, dlogits, inv_b, B, self.n_per // Cc, Cc, MIXQL_K,
                                          C.byref(npart), st)

@@ -65,7 +65,7 @@ class RVconf:
     return n
 
 
-_OBS_PARAMS = {'bernoulli': 1, 'gaussian': 2, 'gaus': 2, 'normal': 2, 'gaussian_softplus1': 2,
+_OBS_PARAMS = {'bernoulli': 1, 'cbernoulli': 1, 'gaussian': 2, 'gaus': 2, 'normal': 2, 'gaussian_softplus1': 2,
                'qlogistic': 2, 'mixqlogistic': None}
 
 
@@ -88,7 +88,7 @@ def _observation(input_shape, distribution: str, n_components: int = 10) -> Tupl
   if distribution not in _OBS_PARAMS:
     raise ValueError(
         f"observation {distribution!r} is outside this build's scope "
-        f"(supported: bernoulli, gaussian, gaussian_softplus1, qlogistic, mixqlogistic)")
+        f"(supported: bernoulli, cbernoulli, gaussian, gaussian_softplus1, qlogistic, mixqlogistic)")
   name = {'gaus': 'gaussian', 'normal': 'gaussian'}.get(distribution, distribution)
   C = int(input_shape[-1])
   if distribution == 'mixqlogistic':

@@ -293,6 +293,72 @@ class BernoulliObservation:
     return torch.bernoulli(p)
 
 
+class ContinuousBernoulliObservation:
+  """Independent(ContinuousBernoulli(logits), 3) ('cbernoulli', odin/bay/distribution_alias.py:108;
+  ContinuousBernoulliLayer, odin/bay/layers/discrete.py:82-121) in logit space, as the HIP kernel evaluates it:
+  log p(x | l) = x l - A(l) with A(l) = log((e^l - 1) / l), mean mu = A'.  Below |l| = 1 both come from their five-term
+  series (A(0) = 0 and mu(0) = 1/2 exactly), above it from the closed forms; the reference's `lims` band around
+  probs = 1/2 has no counterpart."""
+  SWITCH = 1.0
+
+  def __init__(self, logits: torch.Tensor):
+    self.logits = logits
+
+  event_shape = property(lambda self: tuple(self.logits.shape[1:]))
+  batch_shape = property(lambda self: (self.logits.shape[0],))
+  probs = property(lambda self: torch.sigmoid(self.logits))
+
+  def _parts(self):
+    """(small, |l| with the small entries replaced by 1, l^2)"""
+    l = self.logits
+    a = l.abs()
+    small = a < self.SWITCH
+    return small, torch.where(small, torch.ones_like(a), a), l * l
+
+  def log_normalizer(self):
+    """A(l), elementwise"""
+    l = self.logits
+    small, a, l2 = self._parts()
+    ser = 0.5 * l + l2 * (1 / 24 + l2 * (-1 / 2880 + l2 * (1 / 181440 - l2 / 9676800)))
+    closed = torch.clamp(l, min=0) + torch.log1p(-torch.exp(-a)) - torch.log(a)
+    return torch.where(small, ser, closed)
+
+  def mean(self):
+    l = self.logits
+    small, a, l2 = self._parts()
+    ser = 0.5 + l * (1 / 12 + l2 * (-1 / 720 + l2 * (1 / 30240 - l2 / 1209600)))
+    e = torch.exp(-a)
+    om = 1 - e
+    r = 1 / (a * om)
+    closed = torch.clamp(torch.where(l >= 0, a - om, om - a * e) * r, max=1.0)
+    return torch.where(small, ser, closed)
+
+  def log_prob(self, x):
+    # as the kernel: above the switch x l - max(l, 0) is taken as (x - 1) l on the positive side, where the two terms
+    # cancel (x = 1, l = 1e4: log p = 9.2 against terms of 1e4), and A(l) - max(l, 0) = log((1 - e^-|l|) / |l|)
+    l = self.logits
+    small, a, l2 = self._parts()
+    ser = 0.5 * l + l2 * (1 / 24 + l2 * (-1 / 2880 + l2 * (1 / 181440 - l2 / 9676800)))
+    rest = torch.log1p(-torch.exp(-a)) - torch.log(a)
+    xx = torch.where(small | (l < 0), x, x - 1)
+    e = xx * l - torch.where(small, ser, rest)
+    return e.reshape(e.shape[0], -1).sum(1)
+
+  def sample(self, n=None):
+    """inverse CDF: x = 1 + log(u + (1 - u) e^-l) / l for l > 0, 1 - icdf(1 - u; -l) for l < 0, x = u at l = 0"""
+    l = self.logits
+    if n is not None:
+      l = l.unsqueeze(0).expand((int(n),) + tuple(l.shape))
+    u = torch.rand(l.shape, device=l.device, dtype=l.dtype)
+    a = l.abs()
+    flat = a < 1e-30
+    a = torch.where(flat, torch.ones_like(a), a)
+    v = torch.where(l >= 0, u, 1 - u)
+    y = 1 + torch.log1p((1 - v) * torch.expm1(-a)) / a
+    y = torch.where(l >= 0, y, 1 - y)
+    return torch.where(flat, u, y).clamp(0.0, 1.0)
+
+
 class GaussianObservation:
   """Independent(Normal(loc, scale), 3), params split on the channel axis
   (image_networks.py:95-102); softplus1 scale as GaussianLayer (continuous.py:196-260)."""
@@ -702,6 +768,8 @@ class VariationalAutoencoder:
   def _observation_dist(self, h: torch.Tensor):
     if self.observation.posterior == 'bernoulli':
       return BernoulliObservation(h)
+    if self.observation.posterior == 'cbernoulli':
+      return ContinuousBernoulliObservation(h)
     if self.observation.posterior == 'qlogistic':
       return QuantizedLogisticObservation(h)
     if self.observation.posterior == 'mixqlogistic':
