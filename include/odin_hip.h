@@ -309,6 +309,51 @@ int odin_latent_concrete_bwd(const float* p, const float* g, const float* z, con
 int odin_latent_concrete_sample_logprob(const float* p, const float* g, float* z, float* logq, float* logp, int n,
                                         int B, int K, float tau, void* stream);
 
+/* ---- latent posterior q(z|x) = RelaxedBernoulli(tau, logits): the binary Concrete latent (latent_binconcrete.hip).
+ * RelaxedBernoulliLayer (odin/bay/layers/discrete.py:346 ff.; RVconf(D, 'relaxedbern' | 'relaxedsigmoid' |
+ * 'relaxedbernoulli', projection=True), odin/bay/distribution_alias.py:111-112) is D INDEPENDENT binary units; the prior
+ * is Independent(Bernoulli(logits = 0)) (random_variable.py:149-154).  p [B, D] are the logits l (no activation), tau > 0
+ * a constant.
+ *   n ~ Logistic(0, 1);  u = (l + n) / tau;  z = sigmoid(u)  (in (0, 1)^D; the decoder's input)
+ *   log q(z) = sum_d [ log tau - n_d - 2 softplus(-n_d) + softplus(u_d) + softplus(-u_d) ]
+ *            = D log tau + sum_d [ S(u_d) - S(n_d) ],  S(x) = |x| + 2 log1p(exp(-|x|))       (the form evaluated)
+ *   log p(z) = -D log 2
+ * All arithmetic stays in u -- log z and log(1 - z) are never taken: where z rounds to exactly 0 or 1 (tau = 0.1) kl,
+ * logq and dp stay finite.
+ * KL as odin_latent_fwd's `analytic`: 0 = the single-sample log q(z) + D log 2 at the z written (helpers.py:267-276; it
+ * may be negative), 1 = the Bernoulli KL of Jang et al., sum_d [pi log pi + (1 - pi) log(1 - pi) + log 2] with
+ * pi = sigmoid(l) (a departure: TFP registers no KL between the two distributions), evaluated per unit as
+ * t tanh t - log cosh t, t = l / 2, in a form that keeps its relative precision at l -> 0.  free_bits (units: D) /
+ * capacity / fbmask act on the per-sample scalar exactly as in odin_latent_fwd.
+ * odin_rng_logistic: out[e] = the Logistic(0, 1) value of `bits`, component e & 3 of Philox counter e >> 2 under
+ *   (seed, step_dev[0]) -- odin_rng_normal's counter scheme.  With m = bits >> 8: m < 2^23: a = (m + 0.5) 2^-24,
+ *   log a - log1p(-a); otherwise the exact complement c = (2^24 - m - 0.5) 2^-24, log1p(-c) - log c.  Every value is
+ *   finite, |out| <= 25 ln 2 < 17.33, and the map is exactly antisymmetric in m <-> 2^24 - 1 - m.
+ * odin_latent_relaxedbern_fwd: draw = 0 reads the noise n [B, D]; draw = 1 draws it in the kernel -- bit for bit the
+ *   stream odin_rng_logistic writes for (seed, step_dev) -- and STORES it to n (VAEEngine._latent_fwd: the step needs no
+ *   RNG launch).  Writes z [B, D], kl [B], fbmask [B].
+ * odin_latent_relaxedbern_bwd (VAEEngine._backward_enc), with w = klw[0] fbmask_b, G = dz + dz_extra (either may be
+ *   NULL):
+ *     analytic 0: dl_d = (G_d z_d (1 - z_d) + w (2 z_d - 1)) / tau
+ *     analytic 1: dl_d = G_d z_d (1 - z_d) / tau + w pi_d (1 - pi_d) l_d
+ *   klw is a DEVICE scalar as in odin_latent_bwd (graph replays see the beta schedule).  z (1 - z) and 2 z - 1 are formed
+ *   from u = (l + n) / tau: the noise n is READ, the stored z is not (it may be NULL).  Every element of dp [B, D] is
+ *   written exactly once, no float atomics: bit-reproducible.
+ * odin_latent_relaxedbern_sample_logprob (VariationalAutoencoder.marginal_log_prob): the companion of
+ *   odin_latent_concrete_sample_logprob -- p [B, D], n / z [n_samples, B, D], logq / logp [n_samples, B] (logp is the
+ *   constant -D log 2).
+ * One wave per sample, lane k owns units k, k + 64, k + 128, k + 192.  Limits (-2, nothing launched, no output touched):
+ * 1 <= D <= 255, 1 <= B (n_samples B) <= 2^31 - 16, tau > 0, analytic in {0, 1}. */
+int odin_rng_logistic(float* out, size_t n, uint64_t seed, const int32_t* step_dev, void* stream);
+int odin_latent_relaxedbern_fwd(const float* p, float* n, float* z, float* kl, float* fbmask, int B, int D, float tau,
+                                int analytic, float free_bits, const float* capacity, int draw, uint64_t seed,
+                                const int32_t* step_dev, void* stream);
+int odin_latent_relaxedbern_bwd(const float* p, const float* n, const float* z, const float* dz, const float* dz_extra,
+                                const float* fbmask, const float* klw, float* dp, int B, int D, float tau, int analytic,
+                                void* stream);
+int odin_latent_relaxedbern_sample_logprob(const float* p, const float* n, float* z, float* logq, float* logp,
+                                           int n_samples, int B, int D, float tau, void* stream);
+
 /* ---- the bottleneck as one launch per direction (latent_block.hip): DistributionDense(P -> 2D) ->
  * MVNDiag(loc, softplus(raw)) -> reparameterised sample + KL term -> the decoder's first Dense(D -> N0)
  * (dense_distribution.py DistributionDense; variational_autoencoder.py:515-542; helpers.py:236-286;

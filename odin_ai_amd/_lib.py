@@ -106,6 +106,10 @@ SIGNATURES = {
     'odin_latent_concrete_fwd': [P, P, P, P, P, I, I, F, I, F, P, I, C.c_uint64, P, P],
     'odin_latent_concrete_bwd': [P, P, P, P, P, P, P, P, I, I, F, I, P],
     'odin_latent_concrete_sample_logprob': [P, P, P, P, P, I, I, I, F, P],
+    'odin_rng_logistic': [P, C.c_size_t, C.c_uint64, P, P],
+    'odin_latent_relaxedbern_fwd': [P, P, P, P, P, I, I, F, I, F, P, I, C.c_uint64, P, P],
+    'odin_latent_relaxedbern_bwd': [P, P, P, P, P, P, P, P, I, I, F, I, P],
+    'odin_latent_relaxedbern_sample_logprob': [P, P, P, P, P, I, I, I, F, P],
     'odin_latent_block_rows': [I, I, I, I],
     'odin_latent_block_fwd': [P, P, P, P, P, C.c_uint64, P, P, P, P, P, P, P, P, I, I, I, I, I, I, F, P, P],
     'odin_latent_block_bwd': [P, P, P, P, P, P, P, P, P, P, P, P, I, P, P, P, P, P, I, I, I, I, I, P, P],

@@ -590,7 +590,12 @@ class VAEEngine:
       latent_dist     'normal' | 'relaxedonehot': q(z|x) = RelaxedOneHotCategorical(temperature, logits), ONE zdim-way
                       variable; the projection is hdim -> zdim (the logits), `p` / `dp` have that width, `eps` holds the
                       Gumbel noise (train_step's `eps` argument is that noise; None: drawn inside the forward kernel)
-      temperature     its constant temperature (> 0)"""
+      temperature     its constant temperature (> 0)
+    The relaxed Bernoulli (binary Concrete) posterior (latent_binconcrete.hip; the same exclusions and the
+    same unfused slot; 1 <= zdim <= 255):
+      latent_dist     'relaxedbernoulli': q(z|x) = RelaxedBernoulli(temperature, logits), zdim INDEPENDENT binary units;
+                      the projection is hdim -> zdim (the logits), `eps` holds the logistic noise (train_step's `eps`
+                      argument is that noise; None: drawn inside the forward kernel)"""
     self.lib = lib if lib is not None else _lib.load()
     self.device = torch.device(device)
     self.B, self.D = int(batch_size), int(zdim)
@@ -603,8 +608,8 @@ class VAEEngine:
     if latent_cov not in ('diag', 'tril'):
       raise ValueError(f"latent_cov={latent_cov!r}: expected 'diag' or 'tril'")
     self.latent_cov = latent_cov
-    if latent_dist not in ('normal', 'relaxedonehot'):
-      raise ValueError(f"latent_dist={latent_dist!r}: expected 'normal' or 'relaxedonehot'")
+    if latent_dist not in ('normal', 'relaxedonehot', 'relaxedbernoulli'):
+      raise ValueError(f"latent_dist={latent_dist!r}: expected 'normal', 'relaxedonehot' or 'relaxedbernoulli'")
     self.latent_dist, self.temperature = latent_dist, float(temperature)
     self.set_kl_form(analytic, reverse)
     self.free_bits = -1.0 if free_bits is None else float(free_bits)
@@ -635,9 +640,11 @@ class VAEEngine:
       self._check_tril(tc, latent_reg, vamprior_components, vq_codes, range_words, neck_bwd)
     if latent_dist == 'relaxedonehot':
       self._check_concrete(tc, latent_reg, vamprior_components, vq_codes, range_words, neck_bwd)
-    # width of the latent projection: (loc | raw scale), (loc | the D (D + 1) / 2 raw entries of L) or the K logits
+    if latent_dist == 'relaxedbernoulli':
+      self._check_relaxedbern(tc, latent_reg, vamprior_components, vq_codes, range_words, neck_bwd)
+    # width of the latent projection: (loc | raw scale), (loc | the D (D + 1) / 2 raw entries of L) or the logits
     self.pw = self.D + self.D * (self.D + 1) // 2 if latent_cov == 'tril' else 2 * self.D
-    if latent_dist == 'relaxedonehot':
+    if latent_dist in ('relaxedonehot', 'relaxedbernoulli'):
       self.pw = self.D
     f32 = dict(dtype=torch.float32, device=self.device)
     # ---- parameters ----
@@ -762,7 +769,7 @@ class VAEEngine:
       self._plan_chain_fwd(bool(chain_fwd))
       if latent_cov == 'tril':
         self._plan_tril(bool(act_words))
-      elif latent_dist == 'relaxedonehot':
+      elif latent_dist in ('relaxedonehot', 'relaxedbernoulli'):
         # the unfused latent slot only: neither the latent block nor the neck is planned (`neck` is ignored)
         self.lat_block = self._used_block = False
         self.neck = self._used_neck = False
@@ -1145,6 +1152,32 @@ class VAEEngine:
     if neck_bwd:
       raise NotImplementedError(f'{who} with neck_bwd: the fused neck holds the Gaussian latent block')
 
+  # ---- relaxed Bernoulli posterior (latent_binconcrete.hip) ------------------------------------------------
+  def _check_relaxedbern(self, tc, latent_reg, vamprior_components, vq_codes, range_words, neck_bwd):
+    who = "latent_dist='relaxedbernoulli'"
+    if self.latent_cov == 'tril':
+      raise ValueError(f"{who} cannot be combined with latent_cov='tril' (there is no Gaussian scale)")
+    if not 1 <= self.D <= 255:
+      raise ValueError(f'{who}: zdim={self.D} outside the kernel (1 .. 255: four units per lane, and a projection '
+                       f'below the two-plane GEMM)')
+    if not self.temperature > 0.0:
+      raise ValueError(f'{who}: temperature={self.temperature} must be positive')
+    if tc is not None:
+      raise ValueError(f'{who} cannot be combined with tc={tc!r} (the estimator reads a Gaussian posterior)')
+    if latent_reg is not None:
+      raise ValueError(f'{who} cannot be combined with latent_reg={latent_reg!r} (the regularisers compare against a '
+                       f'Gaussian prior sample or read a Gaussian scale)')
+    if vamprior_components is not None:
+      raise ValueError(f"{who} cannot be combined with vamprior_components (the mixture's components are Gaussian)")
+    if vq_codes is not None:
+      raise ValueError(f'{who} cannot be combined with vq_codes (the quantiser has no posterior distribution)')
+    if self.is_dp:
+      raise NotImplementedError(f'{who} under data parallelism (world_size > 1 / force_dp) is not offered')
+    if range_words is not None:
+      raise NotImplementedError(f'{who} on shared range_words is not offered')
+    if neck_bwd:
+      raise NotImplementedError(f'{who} with neck_bwd: the fused neck holds the Gaussian latent block')
+
   def _plan_tril(self, act_words: bool):
     """the unfused latent slot only (`neck` / the latent block are not planned); the two range words of the projection
     where its launches read planes (both widths >= 256 and multiples of 8, a batch of at least 32: D = 29, 32, 45, ...,
@@ -1267,6 +1300,9 @@ class VAEEngine:
     if not reverse and self.latent_dist == 'relaxedonehot':
       raise NotImplementedError("latent_dist='relaxedonehot' with reverse=False: KL(p || q) of a one-hot prior against "
                                 'a density on the simplex is not defined')
+    if not reverse and self.latent_dist == 'relaxedbernoulli':
+      raise NotImplementedError("latent_dist='relaxedbernoulli' with reverse=False: KL(p || q) of a Bernoulli prior "
+                                'against a density on the open unit cube is not defined')
     self.analytic = 2 if not reverse else int(bool(analytic))
 
   def n_params_end(self) -> int:
@@ -1721,13 +1757,15 @@ class VAEEngine:
                                 self.dec.b(0).data_ptr(), self.dec.outs[0].data_ptr(), B, self.hdim, D,
                                 r0.N, ACT[r0.act], int(self.analytic), self.free_bits, cap, st)
       return self.dec.outs[0], 1
-    if self.latent_dist == 'relaxedonehot':
-      # (the Gumbel noise is drawn inside the latent kernel, which leaves it in self.eps: no RNG launch)
+    if self.latent_dist in ('relaxedonehot', 'relaxedbernoulli'):
+      # (the Gumbel / logistic noise is drawn inside the latent kernel, which leaves it in self.eps: no RNG launch)
       h_e = self.enc.forward(x, st)
       lib.odin_dense_fwd(h_e.data_ptr(), lw.data_ptr(), lb.data_ptr(), self.p.data_ptr(), B, self.hdim, self.pw, 0, st)
-      lib.odin_latent_concrete_fwd(self.p.data_ptr(), self.eps.data_ptr(), self.z.data_ptr(), self.kl.data_ptr(),
-                                   self.fbmask.data_ptr(), B, D, self.temperature, int(self.analytic), self.free_bits,
-                                   cap, int(eps is None), self.seed, self.hp(N_HYPER), st)
+      latent_fwd = (lib.odin_latent_concrete_fwd if self.latent_dist == 'relaxedonehot'
+                    else lib.odin_latent_relaxedbern_fwd)
+      latent_fwd(self.p.data_ptr(), self.eps.data_ptr(), self.z.data_ptr(), self.kl.data_ptr(),
+                 self.fbmask.data_ptr(), B, D, self.temperature, int(self.analytic), self.free_bits,
+                 cap, int(eps is None), self.seed, self.hp(N_HYPER), st)
       return self.z, 0
     if eps is None:
       lib.odin_rng_normal(self.eps.data_ptr(), B * D, self.seed, self.hp(N_HYPER), st)
@@ -2103,10 +2141,12 @@ class VAEEngine:
       if bslab is not None:
         jobs.append(self._slab_job(bslab, last.b_off, rows.value))
     else:
-      if self.latent_dist == 'relaxedonehot':
-        lib.odin_latent_concrete_bwd(self.p.data_ptr(), self.eps.data_ptr(), self.z.data_ptr(), self.dz.data_ptr(), dzx,
-                                     self.fbmask.data_ptr(), self.hp(H_KLW), self.dp.data_ptr(), B, D, self.temperature,
-                                     int(self.analytic), st)
+      if self.latent_dist in ('relaxedonehot', 'relaxedbernoulli'):
+        latent_bwd = (lib.odin_latent_concrete_bwd if self.latent_dist == 'relaxedonehot'
+                      else lib.odin_latent_relaxedbern_bwd)
+        latent_bwd(self.p.data_ptr(), self.eps.data_ptr(), self.z.data_ptr(), self.dz.data_ptr(), dzx,
+                   self.fbmask.data_ptr(), self.hp(H_KLW), self.dp.data_ptr(), B, D, self.temperature,
+                   int(self.analytic), st)
       else:
         lib.odin_latent_bwd(self.p.data_ptr(), self.eps.data_ptr(), self.z.data_ptr(),
                             self.dz.data_ptr(), dzx, self.fbmask.data_ptr(), self.hp(H_KLW), tl, ts,

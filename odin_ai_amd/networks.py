@@ -45,7 +45,8 @@ class RVconf:
   """The subset of odin.bay.random_variable.RVconf (random_variable.py:175) the VAE path
   needs: event shape, posterior alias, whether a Dense projection is added, name.  Posterior aliases of the latents
   (distribution_alias.py): 'mvndiag', 'mvntril', and 'relaxedonehot' / 'relaxedsoftmax' -- ONE event_shape[0]-way relaxed
-  one-hot variable whose constant temperature is kwargs['temperature'] (default 0.5)."""
+  one-hot variable whose constant temperature is kwargs['temperature'] (default 0.5) -- and 'relaxedbern' /
+  'relaxedsigmoid' / 'relaxedbernoulli': event_shape[0] independent relaxed Bernoulli units at such a temperature."""
   event_shape: Tuple[int, ...]
   posterior: str = 'mvndiag'
   projection: bool = True

@@ -12,6 +12,7 @@ arguments, method names, returned structures and error behaviour):
   odin/networks/base_networks.py:415-812                  (optimize(), fit())
   odin/bay/layers/continuous.py:459-483                   (latent posteriors 'mvndiag' and 'mvntril')
   odin/bay/layers/discrete.py:286-343                     (latent posterior 'relaxedonehot' / 'relaxedsoftmax')
+  odin/bay/layers/discrete.py:346 ff.                     (latent posterior 'relaxedbern' / 'relaxedsigmoid' / 'relaxedbernoulli')
 
 Tensors are torch tensors on the model's device; returned "distributions" are light
 objects exposing what callers of the reference use (mean / stddev / sample / log_prob /
@@ -59,6 +60,8 @@ class KLdivergence:
       return self._tril(q, analytic, reverse, free_bits, keepdims)
     if isinstance(q, RelaxedOneHotPosterior):
       return self._concrete(q, analytic, reverse, free_bits, keepdims)
+    if isinstance(q, RelaxedBernoulliPosterior):
+      return self._relaxedbern(q, analytic, reverse, free_bits, keepdims)
     if not reverse:  # KL(p || q), helpers.py:261-265
       kl = (torch.log(q.scale) + 0.5 * (1.0 + q.loc ** 2) / q.scale ** 2 - 0.5).sum(-1)
     elif analytic:
@@ -107,6 +110,27 @@ class KLdivergence:
       kl = q.log_prob_cached() + math.log(K) * q.z.sum(-1)
     if free_bits is not None:
       kl = torch.clamp(kl, min=free_bits * K)
+    if analytic and keepdims:
+      kl = kl.unsqueeze(0)
+    return kl
+
+  @staticmethod
+  def _relaxedbern(q: 'RelaxedBernoulliPosterior', analytic, reverse, free_bits, keepdims):
+    if not reverse:
+      raise NotImplementedError(RELAXEDBERN_NO_FORWARD_KL)
+    D = q.logits.shape[-1]
+    if analytic:
+      # (TFP registers no KL between RelaxedBernoulli and Bernoulli: the Bernoulli KL of Jang et al. against the
+      # prior of probability 1/2, per unit t tanh t - log cosh t with t = logits / 2 -- DESIGN 3.18)
+      t = 0.5 * q.logits.abs()
+      th, e = torch.tanh(t), torch.exp(-2.0 * t)
+      # (near 0 the second form is a difference of terms near log 2; above 1 the first one's 1 - tanh^2 cancels)
+      kl = torch.where(t < 1.0, t * th + 0.5 * torch.log1p(-th * th),
+                       math.log(2.0) - torch.log1p(e) - 2.0 * t * e / (1.0 + e)).sum(-1)
+    else:
+      kl = q.log_prob_cached() + D * math.log(2.0)
+    if free_bits is not None:
+      kl = torch.clamp(kl, min=free_bits * D)
     if analytic and keepdims:
       kl = kl.unsqueeze(0)
     return kl
@@ -261,6 +285,76 @@ class RelaxedOneHotPosterior:
   def log_prob_cached(self):
     """log q(z) at the cached sample, from its noise: y = log_softmax((logits + g) / tau)"""
     return self._log_prob_y(torch.log_softmax((self.logits + self.noise) / self.temperature, -1))
+
+  def __array__(self):
+    return self.z.detach().cpu().numpy()
+
+  def tensor(self):
+    """tf.convert_to_tensor(q): the cached sample."""
+    return self.z
+
+
+RELAXEDBERN_NO_FORWARD_KL = ("'relaxedbernoulli' with reverse=False: KL(p || q) of a Bernoulli prior against a density "
+                             'on the open unit cube is not defined')
+
+
+def _softplus_pair(x):
+  """softplus(x) + softplus(-x) = |x| + 2 log1p(exp(-|x|))"""
+  ax = x.abs()
+  return ax + 2.0 * torch.log1p(torch.exp(-ax))
+
+
+class RelaxedBernoulliPosterior:
+  """RelaxedBernoulli(temperature, logits) with its cached sample (odin/bay/layers/discrete.py:346 ff.): D independent
+  binary-concrete units.  p [B, D] are the logits, n [B, D] the logistic noise the cached sample
+  z = sigmoid((logits + n) / tau) was drawn with -- kept so that the cached sample's density is evaluated in
+  u = (logits + n) / tau without taking logit(z): z rounds to exactly 0 or 1 at low temperatures."""
+
+  def __init__(self, p: torch.Tensor, z: torch.Tensor, n: torch.Tensor, temperature: float):
+    self.logits = p
+    self.temperature = float(temperature)
+    self.z, self.noise = z, n
+    self.KL_divergence = KLdivergence(self, prior='Independent(Bernoulli(logits=0))')
+
+  event_shape = property(lambda self: (self.logits.shape[-1],))
+  batch_shape = property(lambda self: tuple(self.logits.shape[:-1]))
+
+  @property
+  def probs(self):
+    return torch.sigmoid(self.logits)
+
+  def mean(self):
+    raise NotImplementedError('RelaxedBernoulli has no closed-form mean (TFP raises too)')
+
+  def _logistic(self, shp, seed=None):
+    g = None
+    if seed is not None:
+      g = torch.Generator(device=self.logits.device).manual_seed(int(seed))
+    u = torch.rand(shp, device=self.logits.device, generator=g).clamp_(2.0 ** -25, 1.0 - 2.0 ** -24)
+    return torch.log(u) - torch.log1p(-u)
+
+  def sample(self, n=None, seed=None):
+    shp = tuple(self.logits.shape) if n is None else (int(n),) + tuple(self.logits.shape)
+    return torch.sigmoid((self.logits + self._logistic(shp, seed)) / self.temperature)
+
+  def _log_prob_u(self, u, noise):
+    """Logistic(logits / tau, 1 / tau).log_prob(u) pushed through Sigmoid; `noise` is its standardised argument
+    tau u - logits"""
+    return (math.log(self.temperature) + _softplus_pair(u) - _softplus_pair(noise)).sum(-1)
+
+  def log_prob(self, z):
+    """the density on the unit cube at z.  The cached sample itself (`q.tensor()`) is evaluated from its noise; at any
+    other z the logit is taken, with entries that rounded to 0 or 1 held one step inside the interval."""
+    if z is self.z:
+      return self.log_prob_cached()
+    fi = torch.finfo(z.dtype)
+    zc = torch.clamp(z, min=fi.tiny, max=1.0 - fi.eps / 2)
+    u = torch.log(zc) - torch.log1p(-zc)
+    return self._log_prob_u(u, self.temperature * u - self.logits)
+
+  def log_prob_cached(self):
+    """log q(z) at the cached sample, from its noise: u = (logits + n) / tau"""
+    return self._log_prob_u((self.logits + self.noise) / self.temperature, self.noise)
 
   def __array__(self):
     return self.z.detach().cpu().numpy()
@@ -557,13 +651,25 @@ class VariationalAutoencoder:
       if not isinstance(net, SequentialNetwork):
         raise ValueError(f'{n} must be a SequentialNetwork description, got {type(net)}')
     posterior = latents.posterior
-    if posterior not in ('mvndiag', 'diag', 'normaldiag', 'mvntril', 'tril', 'relaxedonehot', 'relaxedsoftmax'):
+    if posterior not in ('mvndiag', 'diag', 'normaldiag', 'mvntril', 'tril', 'relaxedonehot', 'relaxedsoftmax',
+                         'relaxedbern', 'relaxedsigmoid', 'relaxedbernoulli'):
       raise ValueError(f"latents posterior {latents.posterior!r} is outside the HIP path "
-                       f"(supported: 'mvndiag', 'mvntril', 'relaxedonehot')")
+                       f"(supported: 'mvndiag', 'mvntril', 'relaxedonehot', 'relaxedbernoulli')")
     self._latent_cov = 'tril' if posterior in ('mvntril', 'tril') else 'diag'
     self._latent_dist = 'relaxedonehot' if posterior in ('relaxedonehot', 'relaxedsoftmax') else 'normal'
-    # (RelaxedOneHotCategoricalLayer's default temperature, discrete.py:286-343)
+    if posterior in ('relaxedbern', 'relaxedsigmoid', 'relaxedbernoulli'):
+      self._latent_dist = 'relaxedbernoulli'
+    # (the default temperature of RelaxedOneHotCategoricalLayer and RelaxedBernoulliLayer, discrete.py:286-343, 346 ff.)
     self._temperature = float(latents.kwargs.get('temperature', 0.5))
+    if self._latent_dist == 'relaxedbernoulli':
+      if self._relaxedbern_refusal is not None:
+        raise ValueError(f"{type(self).__name__} with a 'relaxedbernoulli' posterior: {self._relaxedbern_refusal}")
+      if len(tuple(latents.event_shape)) != 1:
+        raise ValueError(f"'relaxedbernoulli': event_shape={latents.event_shape} must be one axis of binary units")
+      if not self._temperature > 0.0:
+        raise ValueError(f"'relaxedbernoulli': temperature={self._temperature} must be positive")
+      if not reverse:
+        raise NotImplementedError(RELAXEDBERN_NO_FORWARD_KL)
     if self._latent_dist == 'relaxedonehot':
       if self._concrete_refusal is not None:
         raise ValueError(f"{type(self).__name__} with a 'relaxedonehot' posterior: {self._concrete_refusal}")
@@ -703,6 +809,8 @@ class VariationalAutoencoder:
       raise NotImplementedError("'mvntril' with reverse=False: KL(p || q) needs the inverse of L")
     if reverse is not None and not reverse and self._latent_dist == 'relaxedonehot':
       raise NotImplementedError(CONCRETE_NO_FORWARD_KL)
+    if reverse is not None and not reverse and self._latent_dist == 'relaxedbernoulli':
+      raise NotImplementedError(RELAXEDBERN_NO_FORWARD_KL)
     if analytic is not None:
       self.analytic = bool(analytic)
     if reverse is not None:
@@ -757,11 +865,16 @@ class VariationalAutoencoder:
   _tril_refusal: Optional[str] = None
   # the same for the relaxed one-hot posterior ('relaxedonehot')
   _concrete_refusal: Optional[str] = None
+  # and for the relaxed Bernoulli posterior ('relaxedbernoulli')
+  _relaxedbern_refusal: Optional[str] = None
 
   # ------------------------------------------------------------------ forward API
-  def _posterior(self, eng: VAEEngine) -> Union[MVNDiagPosterior, MVNTriLPosterior, RelaxedOneHotPosterior]:
+  def _posterior(self, eng: VAEEngine) -> Union[MVNDiagPosterior, MVNTriLPosterior, RelaxedOneHotPosterior,
+                                                RelaxedBernoulliPosterior]:
     if self._latent_dist == 'relaxedonehot':
       return RelaxedOneHotPosterior(eng.p.clone(), eng.z.clone(), eng.eps.clone(), self._temperature)
+    if self._latent_dist == 'relaxedbernoulli':
+      return RelaxedBernoulliPosterior(eng.p.clone(), eng.z.clone(), eng.eps.clone(), self._temperature)
     cls = MVNTriLPosterior if self._latent_cov == 'tril' else MVNDiagPosterior
     return cls(eng.p.clone(), eng.z.clone(), eng.D)
 
@@ -789,8 +902,8 @@ class VariationalAutoencoder:
 
   def decode(self, latents, training=None, mask=None, only_decoding=False, **kwargs):
     """variational_autoencoder.py:316-360"""
-    z = latents.tensor() if isinstance(latents, (MVNDiagPosterior, MVNTriLPosterior, RelaxedOneHotPosterior)) \
-        else latents
+    z = latents.tensor() if isinstance(latents, (MVNDiagPosterior, MVNTriLPosterior, RelaxedOneHotPosterior,
+                                                 RelaxedBernoulliPosterior)) else latents
     z = _as_tensor(z, self.device)
     eng = self._engine(z.shape[0])
     h = eng.run_decoder(z).clone()
@@ -846,6 +959,8 @@ class VariationalAutoencoder:
     if self._latent_dist == 'relaxedonehot':   # OneHotCategorical with equal logits: one-hot rows
       idx = torch.randint(self.zdim, (int(n),), generator=g)
       return torch.nn.functional.one_hot(idx, self.zdim).to(dtype=torch.float32, device=self.device)
+    if self._latent_dist == 'relaxedbernoulli':   # Independent(Bernoulli(logits=0)): 0 / 1 entries of probability 1/2
+      return torch.randint(2, (int(n), self.zdim), generator=g).to(dtype=torch.float32, device=self.device)
     return torch.randn(int(n), self.zdim, generator=g).to(self.device)
 
   def sample_observation(self, n: int = 1, seed: int = 1, training=False, **kwargs):
@@ -873,9 +988,10 @@ class VariationalAutoencoder:
       eng.set_hyper(beta=1.0, t=self._step, **self._hyper_extra())
       eng.run_encoder(x)  # fills eng.p = (loc | raw scale)
       concrete = self._latent_dist == 'relaxedonehot'
+      relaxedbern = self._latent_dist == 'relaxedbernoulli'
       if eps is None:
         e = torch.empty(n, B, D, **f32)
-        rng = lib.odin_rng_gumbel if concrete else lib.odin_rng_normal
+        rng = lib.odin_rng_gumbel if concrete else lib.odin_rng_logistic if relaxedbern else lib.odin_rng_normal
         rng(e.data_ptr(), n * B * D, self.seed + 7919 + i0, eng.hp(N_HYPER), st)
       else:
         e = _as_tensor(eps, self.device)[:, i0:i0 + B].contiguous()
@@ -884,6 +1000,9 @@ class VariationalAutoencoder:
       if concrete:
         lib.odin_latent_concrete_sample_logprob(eng.p.data_ptr(), e.data_ptr(), z.data_ptr(), lq.data_ptr(),
                                                 lp.data_ptr(), n, B, D, self._temperature, st)
+      elif relaxedbern:
+        lib.odin_latent_relaxedbern_sample_logprob(eng.p.data_ptr(), e.data_ptr(), z.data_ptr(), lq.data_ptr(),
+                                                   lp.data_ptr(), n, B, D, self._temperature, st)
       else:
         sample_logprob = (lib.odin_latent_tril_sample_logprob if self._latent_cov == 'tril'
                           else lib.odin_latent_sample_logprob)
@@ -1299,6 +1418,7 @@ class BetaTCVAE(BetaVAE):
 
   _tril_refusal = 'the total-correlation estimator reads a diagonal scale'
   _concrete_refusal = 'the total-correlation estimator reads a Gaussian posterior'
+  _relaxedbern_refusal = _concrete_refusal
 
   def __init__(self, beta: float = 1.0, name='BetaTCVAE', **kwargs):
     super().__init__(beta=beta, name=name, **kwargs)
@@ -1337,6 +1457,7 @@ class InfoVAE(BetaVAE):
 
   _reg_key = 'div'
   _concrete_refusal = "the MMD's prior sample is Gaussian"
+  _relaxedbern_refusal = _concrete_refusal
 
   def _reg_options(self) -> dict:
     return dict(latent_reg='mmd', reg_coef=self.lamda - self.beta, mmd_kernel=self.mmd_kernel,
@@ -1360,6 +1481,7 @@ class DIPVAE(BetaVAE):
   _reg_key = 'dip'
   _tril_refusal = 'the disentangled-inferred-prior penalty reads a diagonal scale'
   _concrete_refusal = 'the disentangled-inferred-prior penalty reads a Gaussian mean and scale'
+  _relaxedbern_refusal = _concrete_refusal
 
   def _reg_options(self) -> dict:
     return dict(latent_reg='dip_i' if self.only_mean else 'dip_ii', reg_coef=1.0,
@@ -1437,6 +1559,7 @@ class VampriorVAE(BetaVAE):
 
   _tril_refusal = "the mixture's components read a diagonal scale"
   _concrete_refusal = "the mixture's components are Gaussian"
+  _relaxedbern_refusal = _concrete_refusal
 
   def __init__(self, n_components: int = 500, pseudoinputs_mean: float = -0.05, pseudoinputs_std: float = 0.01,
                beta: Union[float, Interpolation] = linear(vmin=1e-6, vmax=1., steps=2000, delay_in=0),
@@ -1607,6 +1730,7 @@ class VQVAE(BetaVAE):
 
   _tril_refusal = 'the quantised latent has no Gaussian posterior'
   _concrete_refusal = 'the quantised latent has no posterior distribution'
+  _relaxedbern_refusal = _concrete_refusal
 
   def __init__(self, n_codes: int = 64, commitment_weight: float = 0.25, distance_metric: str = 'euclidean',
                trainable_prior: bool = False, ema_decay: float = 0.99, ema_update: bool = False,
@@ -1848,6 +1972,7 @@ class FactorVAE(AnnealingVAE):
 
   _tril_refusal = 'its forward-only second engine shares range words, which the triangular path does not offer'
   _concrete_refusal = 'its forward-only second engine shares range words, which the relaxed one-hot path does not offer'
+  _relaxedbern_refusal = 'its forward-only second engine shares range words, which the relaxed Bernoulli path does not offer'
 
   def __init__(self, discriminator_units: Sequence[int] = (1000,) * 5, discriminator_optim=None,
                activation: str = 'relu', batchnorm: bool = False, tc_coef: float = 7.0,
