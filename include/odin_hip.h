@@ -873,6 +873,26 @@ int odin_debug_smallc_planes(int enable);
  * returns the previous value, a negative argument only reads it */
 int odin_debug_igemm_h_ldsw_steps(int steps);
 
+/* ---- TwoStageVAE's skip heads (stage2.hip; odin/bay/vi/autoencoder/two_stage_vae.py, odin/bay/layers/latents.py:23-45):
+ * Dense over Concatenate([x, h]) without the concatenated tensor,
+ *   p [B, N] = x [B, Dx] w[:Dx] + h [B, H] w[Dx:] + bias,   w [(Dx + H), N] row-major (a Dense kernel).
+ * mode 0: p only (`Latents2`: odin_latent_fwd follows).
+ * mode 1 (`Observation2` as a likelihood): N = 2 E, target t [B, E]; the same launch also writes
+ *   llk[b] = sum_e log N(t[b, e]; p[b, e], softplus(p[b, E + e]))   and   dp [B, 2 E] = -scale[0] * d llk / d p
+ *   (scale a DEVICE scalar; softplus and its derivative are finite for raw values in [-80, 80]).
+ * Limits: B >= 1, 1 <= Dx <= 128, N even with 1 <= N / 2 <= 128, H a multiple of 4 in [4, 4096]; anything else returns
+ * -2.  bias may be NULL.  Every sum runs in a fixed order (no float atomics): two calls give the same bits. */
+int odin_skip_head_fwd(const float* x, const float* h, const float* w, const float* bias, float* p, int mode,
+                       const float* target, const float* scale, float* llk, float* dp, int B, int Dx, int H, int N,
+                       void* stream);
+/* From dp [B, N]:  dh [B, H] = (dp w[Dx:]^T) * act'(h) with h the activation's OUTPUT (h_act: 0 linear, 1 elu, 2 relu),
+ * max |dh| folded into dh_amax (a range word, optional);  dx [B, Dx] = dp w[:Dx]^T (optional: NULL where x is data);
+ * slab[g][(Dx + H) N | N]: per-workgroup partial (dW | db), to be summed by odin_slab_reduce -- *slab_rows_out rows, at
+ * most 32.  slab == NULL = dry run (the row count only).  Limits and the fixed summation order as odin_skip_head_fwd. */
+int odin_skip_head_bwd(const float* x, const float* h, const float* w, const float* dp, int h_act, float* dh,
+                       uint32_t* dh_amax, float* dx, float* slab, int* slab_rows_out, int B, int Dx, int H, int N,
+                       void* stream);
+
 /* ---- HIP-graph helpers (capture a sequence of the calls above, replay per step) ------- */
 int odin_graph_begin(void* stream);
 int odin_graph_end(void* stream, void** graph_exec_out);

@@ -1,4 +1,4 @@
-"""VariationalAutoencoder / BetaVAE / AnnealingVAE / BetaTCVAE / FactorVAE / InfoVAE / DIPVAE on the HIP engine.
+"""VariationalAutoencoder / BetaVAE / AnnealingVAE / BetaTCVAE / FactorVAE / InfoVAE / DIPVAE / TwoStageVAE on the HIP engine.
 
 Drop-in for the reference's model API on this path (same class names, constructor
 arguments, method names, returned structures and error behaviour):
@@ -9,6 +9,7 @@ arguments, method names, returned structures and error behaviour):
   odin/bay/vi/autoencoder/factor_vae.py:99                (FactorVAE, two-step training)
   odin/bay/vi/autoencoder/info_vae.py:28-91               (InfoVAE: maximum-mean discrepancy)
   odin/bay/vi/autoencoder/dip_vae.py                      (DIPVAE: disentangled inferred prior)
+  odin/bay/vi/autoencoder/two_stage_vae.py                (TwoStageVAE: a second VAE over the latents)
   odin/networks/base_networks.py:415-812                  (optimize(), fit())
   odin/bay/layers/continuous.py:459-483                   (latent posteriors 'mvndiag' and 'mvntril')
   odin/bay/layers/discrete.py:286-343                     (latent posterior 'relaxedonehot' / 'relaxedsoftmax')
@@ -1090,6 +1091,10 @@ class VariationalAutoencoder:
     """True when a training step met non-finite gradients and skipped its update (host sync)."""
     return any(int(e.flag.item()) != 0 for e in self._engines.values())
 
+  def _nan_flags(self, eng: VAEEngine) -> List[torch.Tensor]:
+    """the device flags `fit` polls for the step it just ran (TwoStageVAE: the second optimiser's in stage 2)"""
+    return [eng.flag]
+
   @property
   def skipped_update(self) -> int:
     """Networks.skipped_update (base_networks.py:573-577): updates zeroed by skip_update_threshold."""
@@ -1244,14 +1249,16 @@ class VariationalAutoencoder:
       # the NaN flag is sticky on device; polling it costs a host sync, so it is read every
       # `nan_check_interval` iterations (and at the end) unless the policy must act at once
       if it % nan_check_interval == 0 or it == max_iter:
-        if int(eng.flag.item()) != 0:  # non-finite gradients: the update was skipped on device
+        flags = self._nan_flags(eng)
+        if any(int(f.item()) != 0 for f in flags):  # non-finite gradients: the update was skipped on device
           if nan_gradients_policy == 'raise':
             raise RuntimeError(f'NaNs gradient! (step {self._step})')
           if nan_gradients_policy == 'stop':
             break
           if nan_gradients_policy == 'restore':  # fall back to the last checkpoint (:543-545)
             self.load_weights(raise_notfound=False)
-          eng.flag.zero_()
+          for f in flags:
+            f.zero_()
         history.append((self._step, float(loss)))
         # Trainer's TensorBoard scalars (training/trainer.py:52-71), at most every logging_interval seconds
         if logdir is not None and now - last_log >= float(logging_interval):
@@ -2408,11 +2415,498 @@ class FactorVAE(AnnealingVAE):
     return disc.dtc[0].clone()
 
 
+# ======================================================================================
+# TwoStageVAE
+# ======================================================================================
+SKIP_HEAD_DMAX = 128    # include/odin_hip.h: odin_skip_head_fwd (Dx and N / 2)
+SKIP_HEAD_HMAX = 4096   # (H, a multiple of 4)
+# stage-2 hyper block (DEVICE floats): Adam {alpha_t, beta1, beta2, eps, grad_scale} | {beta = 1, tc_coef = 0} of
+# odin_elbo_finalize | 1 / B (the heads' `scale`, the latent kernel's `klw`) | the step (int32, odin_rng_normal)
+S2_ALPHA, S2_BETA, S2_INVB, S2_STEP, S2_HYPER = 0, 5, 7, 8, 12
+
+
+class Stage2Network:
+  """two_stage_vae.py:68-97: encoder2 = z -> [Dense(units_i, act)] -> Concatenate([z, h]), latents2 = MVNDiagLatents(Du),
+  decoder2 = u -> [Dense(units[::-1]_i, act)] -> Concatenate([u, g]), observation2 = MVNDiagLatents(D).  ONE set of flat
+  parameter / gradient / Adam buffers with its own iteration count (the second optimiser); `bind(B)` adds the launch
+  programs of a batch size.  The two projections over a concatenation are the skip heads of stage2.hip."""
+
+  def __init__(self, lib, zdim: int, zdim2: int, units: Sequence[int], activation: str, device, seed: int):
+    units = tuple(int(u) for u in units)
+    self.check_limits(zdim, zdim2, units)
+    self.lib, self.device, self.D, self.Du, self.units, self.act = lib, device, int(zdim), int(zdim2), units, activation
+    self.layout = ParamLayout()
+    self.enc_recs, _ = build_layers('encoder2', [('dense', u, activation) for u in units], (self.D,), self.layout)
+    self.dec_recs, _ = build_layers('decoder2', [('dense', u, activation) for u in units[::-1]], (self.Du,), self.layout)
+    self.He, self.Hd = units[-1], units[0]
+    # (kernel | bias contiguous: one slab reduction writes a head's (dW | db) in place; the kernels start on 16-byte
+    # boundaries: the heads then read them with 16-byte loads)
+    self.lat_shape, self.obs_shape = (self.D + self.He, 2 * self.Du), (self.Du + self.Hd, 2 * self.D)
+    self.layout.pad_to(4)
+    self.lat_w_off = self.layout.add(('latents2', 'w'), self.lat_shape)
+    self.lat_b_off = self.layout.add(('latents2', 'b'), (2 * self.Du,))
+    self.layout.pad_to(4)
+    self.obs_w_off = self.layout.add(('observation2', 'w'), self.obs_shape)
+    self.obs_b_off = self.layout.add(('observation2', 'b'), (2 * self.D,))
+    self.layout.pad_to(4)
+    f32 = dict(dtype=torch.float32, device=device)
+    n = self.layout.size
+    self.params, self.grads = torch.zeros(n, **f32), torch.zeros(n, **f32)
+    self.m, self.v = torch.zeros(n, **f32), torch.zeros(n, **f32)
+    g = torch.Generator(device='cpu').manual_seed(seed + 13)
+    for key, shp, off in self.layout.entries:
+      if key[-1] != 'w':   # zero biases
+        continue
+      cnt = int(np.prod(shp))
+      if key[0] in ('latents2', 'observation2'):   # DistributionDense: glorot_normal (dense_distribution.py:124)
+        w = torch.randn(cnt, generator=g) * math.sqrt(2.0 / (shp[0] + shp[1]))
+      else:                                        # Keras Dense default: glorot_uniform
+        w = (torch.rand(cnt, generator=g) * 2 - 1) * math.sqrt(6.0 / (shp[0] + shp[1]))
+      self.params[off:off + cnt] = w.to(device)
+    self.flag = torch.zeros(1, dtype=torch.int32, device=device)
+    self.t = 0   # iterations of the second stage's own Adam
+    self.bound: Dict[int, 'Stage2Programs'] = {}
+
+  @staticmethod
+  def check_limits(zdim: int, zdim2: int, units: Sequence[int]):
+    """the regime of odin_skip_head_fwd / _bwd (include/odin_hip.h), named when the model is built"""
+    if len(units) < 1:
+      raise ValueError('TwoStageVAE: stage2_units must name at least one hidden layer (the skip heads read the last one)')
+    for what, d in (('the first stage\'s zdim', zdim), ('stage2_zdim', zdim2)):
+      if not 1 <= int(d) <= SKIP_HEAD_DMAX:
+        raise ValueError(f'TwoStageVAE: {what} = {d} is outside the skip heads\' limit 1 <= D <= {SKIP_HEAD_DMAX}')
+    for what, h in (('stage2_units[-1]', units[-1]), ('stage2_units[0]', units[0])):
+      if h < 4 or h % 4 != 0 or h > SKIP_HEAD_HMAX:
+        raise ValueError(f'TwoStageVAE: {what} = {h} is outside the skip heads\' limit: the hidden width a head reads '
+                         f'must be a multiple of 4 in [4, {SKIP_HEAD_HMAX}]')
+    if any(u < 1 for u in units):
+      raise ValueError(f'TwoStageVAE: stage2_units = {tuple(units)} must be positive')
+
+  @property
+  def n_parameters(self):
+    return sum(int(np.prod(s)) for _, s, _ in self.layout.entries)
+
+  def names(self):
+    """[(checkpoint name, flat offset, shape)]: the Keras names of the four stage-2 layers (two_stage_vae.py:79-92)"""
+    out = []
+    for key, shp, off in self.layout.entries:
+      suffix = 'kernel' if key[-1] == 'w' else 'bias'
+      if key[0] in ('latents2', 'observation2'):
+        out.append((f'{key[0]}/{suffix}', off, shp))
+      else:
+        out.append((f"{key[0]}/{'Encoder2' if key[0] == 'encoder2' else 'Decoder2'}_{key[1]}/{suffix}", off, shp))
+    return out
+
+  def bind(self, B: int) -> 'Stage2Programs':
+    if B not in self.bound:
+      self.bound[B] = Stage2Programs(self, B)
+    return self.bound[B]
+
+
+class Stage2Programs:
+  """Launch programs + activation buffers of the second stage for one batch size: two NetPrograms (the dense stacks),
+  the two skip heads, odin_latent_fwd / _bwd for q(u|z), odin_slab_reduce and the second optimiser's Adam."""
+
+  def __init__(self, net: Stage2Network, B: int):
+    lib, device, D, Du = net.lib, net.device, net.D, net.Du
+    f32 = dict(dtype=torch.float32, device=device)
+    self.net, self.B = net, B
+    mr = lib.odin_max_slab_rows()
+    ne, nd = len(net.enc_recs) * RANGE_WORDS, len(net.dec_recs) * RANGE_WORDS
+    # (gradient words of the two stacks | their activation words: cleared once per step, reset_job)
+    self.range_words = torch.zeros(2 * (ne + nd), dtype=torch.int32, device=device)
+    rw = self.range_words
+    self.enc = NetProgram(lib, net.enc_recs, B, device, net.params, net.grads, mr, range_words=rw[:ne],
+                          act_words=rw[ne + nd:2 * ne + nd])
+    self.dec = NetProgram(lib, net.dec_recs, B, device, net.params, net.grads, mr, range_words=rw[ne:ne + nd],
+                          act_words=rw[2 * ne + nd:])
+    # (the heads' backward leaves dh = the stacks' top gradients with their range words)
+    self.enc.set_top_word(True)
+    self.dec.set_top_word(True)
+    self.p2, self.dp2 = torch.zeros(B, 2 * Du, **f32), torch.zeros(B, 2 * Du, **f32)   # q(u|z): (loc | raw scale)
+    self.eps2, self.u = torch.zeros(B, Du, **f32), torch.zeros(B, Du, **f32)
+    self.kl2, self.fbmask = torch.zeros(B, **f32), torch.zeros(B, **f32)
+    self.du_head, self.du_stack = torch.zeros(B, Du, **f32), torch.zeros(B, Du, **f32)
+    self.po, self.dpo = torch.zeros(B, 2 * D, **f32), torch.zeros(B, 2 * D, **f32)     # p(z|u): (loc | raw scale)
+    self.llk_raw, self.llk = torch.zeros(B, **f32), torch.zeros(B, **f32)
+    self.eps3, self.zs = torch.zeros(B, D, **f32), torch.zeros(B, D, **f32)            # a sample of q(z|u)
+    self.kl_unused, self.mask_unused = torch.zeros(B, **f32), torch.zeros(B, **f32)
+    self.out4 = torch.zeros(4, **f32)   # loss | mean llk | mean kl | 0
+    self.hyper = torch.zeros(S2_HYPER, **f32)
+    self._hyper_host = torch.zeros(S2_HYPER, dtype=torch.float32)
+    self.ws, self.gnorm2 = torch.zeros(1024, **f32), torch.zeros(1, **f32)
+    rows = C.c_int(0)
+    lib.odin_skip_head_bwd(None, None, None, None, 0, None, None, None, None, C.byref(rows), B, D, net.He, 2 * Du, None)
+    self.lat_slab = torch.empty(rows.value, net.lat_shape[0] * net.lat_shape[1] + 2 * Du, **f32)
+    lib.odin_skip_head_bwd(None, None, None, None, 0, None, None, None, None, C.byref(rows), B, Du, net.Hd, 2 * D, None)
+    self.obs_slab = torch.empty(rows.value, net.obs_shape[0] * net.obs_shape[1] + 2 * D, **f32)
+    self._words_dirty = False
+    self._keep = None
+
+  def hp(self, idx: int) -> int:
+    return self.hyper.data_ptr() + 4 * idx
+
+  def stream(self):
+    if self.net.device.type == 'cuda':
+      return torch.cuda.current_stream(self.net.device).cuda_stream
+    return None
+
+  def set_hyper(self, step: int, optim: Optional[dict] = None):
+    """host scalars -> device; `optim`: the second optimiser's (learning_rate, beta_1, beta_2, epsilon) for the update
+    that follows (its bias correction reads the network's own iteration count)"""
+    h = self._hyper_host
+    h.zero_()
+    if optim is not None:
+      t = self.net.t + 1
+      b1, b2 = optim['beta_1'], optim['beta_2']
+      h[S2_ALPHA] = optim['learning_rate'] * math.sqrt(1.0 - b2 ** t) / (1.0 - b1 ** t)
+      h[S2_ALPHA + 1], h[S2_ALPHA + 2], h[S2_ALPHA + 3], h[S2_ALPHA + 4] = b1, b2, optim['epsilon'], 1.0
+    h[S2_BETA] = 1.0   # (beta is not applied in stage 2: TwoStageVAE.elbo_components bypasses BetaVAE's scaling)
+    h[S2_INVB] = 1.0 / self.B
+    h[S2_STEP:].view(torch.int32)[0] = int(step)
+    self.hyper.copy_(h)
+
+  def _w(self, off, shp):
+    return self.net.params[off:off + shp[0] * shp[1]].data_ptr()
+
+  def _b(self, off):
+    return self.net.params[off:].data_ptr()
+
+  def _reset_words(self, st):
+    self.net.lib.odin_range_reset(self.range_words.data_ptr(), self.range_words.numel() // RANGE_WORDS, st)
+
+  def encode(self, z: torch.Tensor, eps2: Optional[torch.Tensor], seed: int, analytic: int, free_bits: float, st):
+    """z -> encoder2 -> Latents2: p2, u = loc + softplus(raw) * eps2, kl2, fbmask"""
+    lib, net, B = self.net.lib, self.net, self.B
+    he = self.enc.forward(z, st)
+    lib.odin_skip_head_fwd(z.data_ptr(), he.data_ptr(), self._w(net.lat_w_off, net.lat_shape), self._b(net.lat_b_off),
+                           self.p2.data_ptr(), 0, None, None, None, None, B, net.D, net.He, 2 * net.Du, st)
+    if eps2 is None:
+      lib.odin_rng_normal(self.eps2.data_ptr(), B * net.Du, seed, self.hp(S2_STEP), st)
+    elif eps2 is not self.eps2:
+      self.eps2.copy_(eps2)
+    lib.odin_latent_fwd(self.p2.data_ptr(), self.eps2.data_ptr(), self.u.data_ptr(), self.kl2.data_ptr(),
+                        self.fbmask.data_ptr(), B, net.Du, analytic, free_bits, None, st)
+
+  def decode(self, u: torch.Tensor, target: Optional[torch.Tensor], st):
+    """u -> decoder2 -> Observation2: po; with a target also llk_raw = log p(target | u) and dpo = -d llk / d po / B"""
+    lib, net, B = self.net.lib, self.net, self.B
+    hd = self.dec.forward(u, st)
+    if target is None:
+      lib.odin_skip_head_fwd(u.data_ptr(), hd.data_ptr(), self._w(net.obs_w_off, net.obs_shape), self._b(net.obs_b_off),
+                             self.po.data_ptr(), 0, None, None, None, None, B, net.Du, net.Hd, 2 * net.D, st)
+    else:
+      lib.odin_skip_head_fwd(u.data_ptr(), hd.data_ptr(), self._w(net.obs_w_off, net.obs_shape), self._b(net.obs_b_off),
+                             self.po.data_ptr(), 1, target.data_ptr(), self.hp(S2_INVB), self.llk_raw.data_ptr(),
+                             self.dpo.data_ptr(), B, net.Du, net.Hd, 2 * net.D, st)
+
+  def sample_observation2(self, eps3: Optional[torch.Tensor], seed: int, st):
+    """zs = a sample of q(z|u) = MVNDiag(po)"""
+    lib, net, B = self.net.lib, self.net, self.B
+    if eps3 is None:
+      lib.odin_rng_normal(self.eps3.data_ptr(), B * net.D, seed, self.hp(S2_STEP), st)
+    else:
+      self.eps3.copy_(eps3)
+    lib.odin_latent_fwd(self.po.data_ptr(), self.eps3.data_ptr(), self.zs.data_ptr(), self.kl_unused.data_ptr(),
+                        self.mask_unused.data_ptr(), B, net.D, 0, -1.0, None, st)
+
+  def forward(self, z, eps2, seed, analytic, free_bits, st, for_step: bool = False):
+    """the stage-2 ELBO of z: llk [B], kl2 [B], out4 = (loss, mean llk, mean kl, 0)"""
+    if self._words_dirty or not for_step:   # (a step's own reset rides in its slab reduction)
+      self._reset_words(st)
+    self._words_dirty = not for_step
+    self.encode(z, eps2, seed, analytic, free_bits, st)
+    self.decode(self.u, z, st)
+    self.net.lib.odin_elbo_finalize(self.llk_raw.data_ptr(), 1, self.kl2.data_ptr(), self.hp(S2_BETA), None,
+                                    self.llk.data_ptr(), self.out4.data_ptr(), self.B, st)
+
+  def backward(self, z, analytic, st):
+    """gradients of out4[0] with respect to every stage-2 parameter -> net.grads (z is data: no gradient leaves)"""
+    lib, net, B = self.net.lib, self.net, self.B
+    act = ACT[net.act]
+    ne, nd = len(net.enc_recs), len(net.dec_recs)
+    orows, lrows = C.c_int(0), C.c_int(0)
+    lib.odin_skip_head_bwd(self.u.data_ptr(), self.dec.outs[-1].data_ptr(), self._w(net.obs_w_off, net.obs_shape),
+                           self.dpo.data_ptr(), act, self.dec.gouts[-1].data_ptr(), self.dec.word(nd - 1),
+                           self.du_head.data_ptr(), self.obs_slab.data_ptr(), C.byref(orows), B, net.Du, net.Hd,
+                           2 * net.D, st)
+    jobs = self.dec.backward(self.u, self.dec.gouts[-1], st, dx_out=self.du_stack)
+    lib.odin_latent_bwd(self.p2.data_ptr(), self.eps2.data_ptr(), self.u.data_ptr(), self.du_head.data_ptr(),
+                        self.du_stack.data_ptr(), self.fbmask.data_ptr(), self.hp(S2_INVB), None, None,
+                        self.dp2.data_ptr(), B, net.Du, analytic, st)
+    lib.odin_skip_head_bwd(z.data_ptr(), self.enc.outs[-1].data_ptr(), self._w(net.lat_w_off, net.lat_shape),
+                           self.dp2.data_ptr(), act, self.enc.gouts[-1].data_ptr(), self.enc.word(ne - 1), None,
+                           self.lat_slab.data_ptr(), C.byref(lrows), B, net.D, net.He, 2 * net.Du, st)
+    jobs += self.enc.backward(z, self.enc.gouts[-1], st)
+    assert 0 < orows.value <= self.obs_slab.shape[0] and 0 < lrows.value <= self.lat_slab.shape[0]
+    for slab, off, rows in ((self.obs_slab, net.obs_w_off, orows.value), (self.lat_slab, net.lat_w_off, lrows.value)):
+      jobs.append(ReduceJob(slab.data_ptr(), net.grads[off:].data_ptr(), slab.shape[1], rows, slab.shape[1], 0))
+    rw = self.range_words   # (zero the range words: a reduction over zero slab rows, as DiscPrograms.reset_job)
+    jobs.append(ReduceJob(rw.data_ptr(), rw.data_ptr(), rw.numel(), 0, rw.numel(), 0))
+    arr = (ReduceJob * len(jobs))(*jobs)
+    self._keep = arr
+    lib.odin_slab_reduce(arr, len(jobs), st)
+
+  def adam(self, check_nan: bool, st):
+    lib, net = self.net.lib, self.net
+    if check_nan:   # the gradient norm is the NaN guard: a non-finite one leaves parameters and moments alone
+      lib.odin_sumsq_adam_flat(net.params.data_ptr(), net.grads.data_ptr(), net.m.data_ptr(), net.v.data_ptr(),
+                               net.params.numel(), self.hp(S2_ALPHA), self.ws.data_ptr(), self.gnorm2.data_ptr(), 0.0,
+                               net.flag.data_ptr(), st)
+    else:
+      lib.odin_adam_step_flat(net.params.data_ptr(), net.grads.data_ptr(), net.m.data_ptr(), net.v.data_ptr(),
+                              net.params.numel(), self.hp(S2_ALPHA), None, 0.0, None, st)
+
+
+class TwoStageVAE(BetaVAE):
+  """two_stage_vae.py:17-216 (Dai & Wipf 2019, "Diagnosing and Enhancing VAE Models"): a second VAE over the latents of
+  the first.  Stage 1 is the BetaVAE it extends -- same engine, same launches.  Stage 2 freezes it: z is the cached sample
+  of q(z|x), q(u|z) = Latents2(encoder2(z)), p(z|u) = Observation2(decoder2(u)), loss = -mean(log p(z|u) - KL(q(u|z) ||
+  N(0, I))), beta not applied; it trains exactly the stage-2 variables with its own Adam (`stage2_optimizer`: None or a
+  dict learning_rate / beta_1 / beta_2 / epsilon; default Adam(1e-4)).  (The reference marks the stage-2 layers
+  non-trainable at construction and never undoes it, so as shipped nothing trains in stage 2: DESIGN 3.19.)
+  Stage-2 noise: keywords `eps` (z), `eps2` (u), `eps3` (the sample of q(z|u)); otherwise drawn on the device from the
+  model's seed and step.  Stage-2 steps are launched eagerly."""
+
+  _tril_refusal = "the second stage models the sample of a diagonal Gaussian q(z|x) ('mvndiag' only)"
+  _concrete_refusal = _tril_refusal
+  _relaxedbern_refusal = _tril_refusal
+
+  def __init__(self, stage2_units: Sequence[int] = (1024, 1024, 1024), stage2_zdim: Optional[int] = None,
+               stage2_iter_ratio: int = 4, stage2_optimizer: Optional[dict] = None, activation: str = 'relu',
+               initializer=None, auto_train_2stages: bool = True, name='TwoStageVAE', **kwargs):
+    if activation not in ACT:
+      raise ValueError(f'TwoStageVAE: activation={activation!r} is outside the HIP path (relu, elu, linear)')
+    if initializer not in (None, 'glorot_uniform'):
+      raise NotImplementedError(f'TwoStageVAE: initializer={initializer!r}; the HIP path draws the Keras default '
+                                '(glorot_uniform, zero biases)')
+    self.stage2_units = tuple(int(u) for u in stage2_units)
+    self._stage2_zdim = None if stage2_zdim is None else int(stage2_zdim)
+    self.stage2_iter_ratio = int(stage2_iter_ratio)
+    self.stage2_optimizer = dict(learning_rate=1e-4, beta_1=0.9, beta_2=0.999, epsilon=1e-7)
+    if stage2_optimizer is not None:
+      unknown = set(stage2_optimizer) - set(self.stage2_optimizer)
+      if unknown:
+        raise ValueError(f'TwoStageVAE: stage2_optimizer keys {sorted(unknown)} (Adam: {sorted(self.stage2_optimizer)})')
+      self.stage2_optimizer.update({k: float(v) for k, v in stage2_optimizer.items()})
+    self.stage2_activation = activation
+    self.auto_train_2stages = bool(auto_train_2stages)
+    self._train_stage1 = self._eval_stage1 = True
+    self._stage2_net: Optional[Stage2Network] = None
+    super().__init__(name=name, **kwargs)
+    Stage2Network.check_limits(self.zdim, self.stage2_zdim, self.stage2_units)
+
+  @property
+  def stage2_zdim(self) -> int:
+    return self.zdim if self._stage2_zdim is None else self._stage2_zdim
+
+  @property
+  def stage2(self) -> Stage2Network:
+    if self._stage2_net is None:
+      eng = self._engine(1)
+      self._stage2_net = Stage2Network(eng.lib, self.zdim, self.stage2_zdim, self.stage2_units, self.stage2_activation,
+                                       self.device, self.seed)
+      from .dist import broadcast_parameters
+      broadcast_parameters(self._stage2_net.params, src=0)
+    return self._stage2_net
+
+  # ---- stages ----
+  def set_train_stage(self, stage: int) -> 'TwoStageVAE':
+    if stage not in (1, 2):
+      raise ValueError(f'stage={stage!r} (1 | 2)')
+    self._train_stage1 = stage == 1
+    return self
+
+  def set_eval_stage(self, stage: int) -> 'TwoStageVAE':
+    if stage not in (1, 2):
+      raise ValueError(f'stage={stage!r} (1 | 2)')
+    self._eval_stage1 = stage == 1
+    return self
+
+  train_stage = property(lambda self: 1 if self._train_stage1 else 2)
+  eval_stage = property(lambda self: 1 if self._eval_stage1 else 2)
+
+  def _kl_form(self) -> Tuple[int, float]:
+    """(odin_latent_fwd's `analytic`, its `free_bits`) of the model's ELBO configuration"""
+    return (2 if not self.reverse else int(self.analytic)), (-1.0 if self.free_bits is None else float(self.free_bits))
+
+  def _stage2_refusals(self):
+    if self.n_samples != 1:
+      raise NotImplementedError(f'TwoStageVAE stage 2 with sample_shape={self.sample_shape}: the second stage reads ONE '
+                                'cached sample of q(z|x) per input (sample_shape=())')
+    if self._world_size() > 1 or bool(getattr(self, 'force_dp', False)):
+      raise NotImplementedError('TwoStageVAE stage 2 under data parallelism: its gradients are not all-reduced '
+                                '(train the second stage on one GPU)')
+
+  def _first_stage(self, x: torch.Tensor, eps) -> Tuple[VAEEngine, Stage2Programs]:
+    """the frozen first stage: run_encoder leaves q(z|x) in eng.p and its sample in eng.z"""
+    eng = self._engine(x.shape[0])
+    eng.set_hyper(beta=self.beta, t=self._step, **self._hyper_extra())
+    eng.run_encoder(x, None if eps is None else _as_tensor(eps, self.device).reshape(x.shape[0], -1))
+    return eng, self.stage2.bind(x.shape[0])
+
+  def _noise(self, e, B, D):
+    return None if e is None else _as_tensor(e, self.device).reshape(B, D)
+
+  # ---- forward API ----
+  def encode(self, inputs, training=None, mask=None, only_encoding=False, eps=None, eps2=None, eps3=None, **kwargs):
+    """two_stage_vae.py:135-159: at eval stage 2 q(z|u) with u ~ q(u|z), z ~ q(z|x)"""
+    if only_encoding or self._eval_stage1:
+      return super().encode(inputs, training=training, mask=mask, only_encoding=only_encoding, eps=eps, **kwargs)
+    return self.encode_two_stages(inputs, training=training, mask=mask, eps=eps, eps2=eps2, eps3=eps3)[2]
+
+  def encode_two_stages(self, inputs, training=None, mask=None, eps=None, eps2=None, eps3=None):
+    """-> (q(z|x), q(u|z), q(z|u)), each with its cached sample (two_stage_vae.py:161-179)"""
+    self._stage2_refusals()
+    x = _as_tensor(inputs, self.device)
+    B = x.shape[0]
+    eng, s2 = self._first_stage(x, eps)
+    qz_x = self._posterior(eng)
+    st = s2.stream()
+    s2.set_hyper(self._step)
+    s2._reset_words(st)
+    s2._words_dirty = True
+    s2.encode(eng.z, self._noise(eps2, B, self.stage2_zdim), self.seed + 17, 0, -1.0, st)
+    s2.decode(s2.u, None, st)
+    s2.sample_observation2(self._noise(eps3, B, self.zdim), self.seed + 19, st)
+    qu_z = MVNDiagPosterior(s2.p2.clone(), s2.u.clone(), self.stage2_zdim)
+    qz_u = MVNDiagPosterior(s2.po.clone(), s2.zs.clone(), self.zdim)
+    return qz_x, qu_z, qz_u
+
+  def elbo_components2(self, inputs, training=None, mask=None, eps=None, eps2=None, **kwargs):
+    """two_stage_vae.py:181-192: ({'llk_<latents>': log p(z|u) [B]}, {'kl_latents2': KL(q(u|z) || p(u)) [B]})"""
+    self._stage2_refusals()
+    x = _as_tensor(inputs, self.device)
+    eng, s2 = self._first_stage(x, eps)
+    analytic, free_bits = self._kl_form()
+    s2.set_hyper(self._step)
+    s2.forward(eng.z, self._noise(eps2, x.shape[0], self.stage2_zdim), self.seed + 17, analytic, free_bits, s2.stream())
+    return {f'llk_{self.latents.name}': s2.llk.clone()}, {'kl_latents2': s2.kl2.clone()}
+
+  def elbo_components(self, inputs, training=None, mask=None, eps=None, **kwargs):
+    if self._train_stage1:
+      return super().elbo_components(inputs, training=training, mask=mask, eps=eps, **kwargs)
+    return self.elbo_components2(inputs, training=training, mask=mask, eps=eps, **kwargs)
+
+  def sample_prior(self, n: int = 1, seed: int = 1, two_stage: bool = True) -> torch.Tensor:
+    """two_stage_vae.py:99-107: u ~ N(0, I) -> decoder2 -> observation2 -> a sample [n, D]"""
+    if not two_stage:
+      return super().sample_prior(n, seed=seed)
+    n = int(n)
+    g = torch.Generator(device='cpu').manual_seed(int(seed))
+    u = torch.randn(n, self.stage2_zdim, generator=g).to(self.device)
+    eps3 = torch.randn(n, self.zdim, generator=g).to(self.device)
+    s2 = self.stage2.bind(n)
+    st = s2.stream()
+    s2.set_hyper(self._step)
+    s2._reset_words(st)
+    s2._words_dirty = True
+    s2.decode(u.contiguous(), None, st)
+    s2.sample_observation2(eps3, 0, st)
+    return s2.zs.clone()
+
+  def sample_observation(self, n: int = 1, seed: int = 1, training=False, two_stage: bool = True, **kwargs):
+    return self.decode(self.sample_prior(n, seed=seed, two_stage=two_stage), training=training)
+
+  # ---- training ----
+  def optimize(self, inputs, training: bool = True, optimizer=None, learning_rate=1e-4, clipnorm=None, clipvalue=None,
+               global_clipnorm=None, skip_update_threshold=None, when_skip_update: int = 0,
+               nan_gradients_policy: str = 'skip', allow_none_gradients=False, aggregate_gradients=False,
+               track_gradients=False, eps=None, use_graph: bool = False, eps2=None):
+    """Stage 1: VariationalAutoencoder.optimize.  Stage 2: the frozen first stage's run_encoder, then the stage-2 step
+    under `stage2_optimizer` (`learning_rate` belongs to the first optimiser and is not read, as the reference's second
+    fit drops it); -> (loss, {'llk_<latents>', 'kl_latents2'}).  The clipping policies are not offered in stage 2."""
+    if self._train_stage1:
+      return super().optimize(inputs, training=training, optimizer=optimizer, learning_rate=learning_rate,
+                              clipnorm=clipnorm, clipvalue=clipvalue, global_clipnorm=global_clipnorm,
+                              skip_update_threshold=skip_update_threshold, when_skip_update=when_skip_update,
+                              nan_gradients_policy=nan_gradients_policy, allow_none_gradients=allow_none_gradients,
+                              aggregate_gradients=aggregate_gradients, track_gradients=track_gradients, eps=eps,
+                              use_graph=use_graph)
+    if nan_gradients_policy not in ('stop', 'skip', 'raise', 'ignore', 'restore'):
+      raise ValueError(f'nan_gradients_policy={nan_gradients_policy!r}')
+    if any(a is not None for a in (clipnorm, clipvalue, global_clipnorm, skip_update_threshold)):
+      raise NotImplementedError('TwoStageVAE stage 2: clipnorm / clipvalue / global_clipnorm / skip_update_threshold are '
+                                'not wired to the second optimiser')
+    self._stage2_refusals()
+    x = _as_tensor(inputs, self.device)
+    if training:
+      self._step += 1
+    eng, s2 = self._first_stage(x, eps)
+    net = s2.net
+    analytic, free_bits = self._kl_form()
+    st = s2.stream()
+    s2.set_hyper(self._step, self.stage2_optimizer if training else None)
+    s2.forward(eng.z, self._noise(eps2, x.shape[0], self.stage2_zdim), self.seed + 17, analytic, free_bits, st,
+               for_step=training)
+    if training:
+      s2.backward(eng.z, analytic, st)
+      s2.adam(nan_gradients_policy != 'ignore', st)
+      net.t += 1
+    out = s2.out4.clone()
+    metrics = {f'llk_{self.latents.name}': out[1], 'kl_latents2': out[2]}
+    if training and track_gradients:
+      for (name, off, shp) in net.names():
+        metrics['_grad/' + name] = net.grads[off:off + int(np.prod(shp))].view(shp).clone()
+    return out[0], metrics
+
+  @property
+  def nan_flag(self) -> bool:
+    s2 = self._stage2_net
+    return super().nan_flag or (s2 is not None and int(s2.flag.item()) != 0)
+
+  def _nan_flags(self, eng) -> List[torch.Tensor]:
+    return [eng.flag] if (self._train_stage1 or self._stage2_net is None) else [self._stage2_net.flag]
+
+  def fit(self, train, *, valid=None, **kwargs):
+    """two_stage_vae.py:202-216: the normal fit; then, still in stage 1 and `auto_train_2stages`, stage 2 for
+    stage2_iter_ratio x the requested max_iter / epochs under the second optimiser, and back to stage 1"""
+    super().fit(train, valid=valid, **kwargs)
+    if self._train_stage1 and self.auto_train_2stages:
+      self.set_train_stage(2)
+      try:
+        for k in ('on_batch_end', 'on_valid_end', 'optimizer', 'learning_rate'):
+          kwargs.pop(k, None)
+        super().fit(train, epochs=kwargs.pop('epochs', -1) * self.stage2_iter_ratio,
+                    max_iter=kwargs.pop('max_iter', 1000) * self.stage2_iter_ratio, **kwargs)
+      finally:
+        self.set_train_stage(1)
+    return self
+
+  # ---- checkpoints: the four stage-2 layers and the second optimiser are attributes of the reference's model ----
+  def _extra_checkpoint_variables(self) -> Dict[str, np.ndarray]:
+    net = self.stage2
+    W = {}
+    for name, off, shp in net.names():
+      n = int(np.prod(shp))
+      W[name] = net.params[off:off + n].view(shp).detach().cpu().numpy()
+      W[f'stage2_optimizer/{name}/m'] = net.m[off:off + n].view(shp).detach().cpu().numpy()
+      W[f'stage2_optimizer/{name}/v'] = net.v[off:off + n].view(shp).detach().cpu().numpy()
+    W['stage2_optimizer/iter'] = np.asarray(net.t, np.int64)
+    return W
+
+  def _load_extra_checkpoint_variables(self, d: Dict[str, np.ndarray]):
+    net = self.stage2
+    names = net.names()
+    if not any(n == nm or n.endswith('/' + nm) for n in d for nm, _, _ in names):
+      return   # a checkpoint of the first stage alone (a BetaVAE's): the second stage keeps what it holds
+    as_t = lambda a: torch.as_tensor(np.asarray(a), dtype=torch.float32, device=self.device)
+    for name, off, shp in names:
+      n = int(np.prod(shp))
+      a = self._find_variable(d, name)
+      if tuple(a.shape) != tuple(shp):
+        raise ValueError(f'{name}: checkpoint shape {a.shape} != {tuple(shp)}')
+      net.params[off:off + n].view(shp).copy_(as_t(a))
+      for slot, buf in (('m', net.m), ('v', net.v)):
+        buf[off:off + n].view(shp).copy_(as_t(self._find_variable(d, f'stage2_optimizer/{name}/{slot}')))
+    net.t = int(self._find_variable(d, 'stage2_optimizer/iter'))
+
+
 def get_vae(name: str):
   """odin/bay/vi/autoencoder/__init__.py:28"""
   table = {c.__name__.lower(): c for c in (VariationalAutoencoder, BetaVAE, AnnealingVAE,
                                            BetaTCVAE, FactorVAE, BetaCapacityVAE, InfoVAE, DIPVAE,
-                                           VampriorVAE, VQVAE)}
+                                           VampriorVAE, VQVAE, TwoStageVAE)}
   table['vae'] = VariationalAutoencoder
   key = str(name).lower().replace('_', '')
   if key not in table:
