@@ -485,6 +485,34 @@ int odin_elbo_bernoulli_fwd_bwd_ranged(const float* logits, const float* x, floa
 int odin_elbo_cbernoulli_fwd_bwd(const float* logits, const float* x, float* llk_part, float* dlogits,
                                  const float* scale, int B, int n_per_sample, int* n_part_out,
                                  uint32_t* dlogits_amax, void* stream);
+/* The count observations of the gene-expression stacks (elbo_counts.hip):
+ * Independent(NegativeBinomial(total_count = exp(a), logits = l), 1).log_prob(x) ('nb'; NegativeBinomialLayer with
+ * dispersion 'full', odin/bay/layers/count_layers.py:75-163) and, with zero_inflated = 1, its zero-inflated form ('zinb';
+ * ZINegativeBinomialLayer, :311-416; odin/bay/distributions/zero_inflated.py:216-230).  params [B, P G], P = 2 +
+ * zero_inflated, holds PLANES of G floats per sample, (a | l) or (a | l | pi) = split(params, P, axis=-1), pi the
+ * inflation logit; x [B, G] the counts.  Per element, with r = e^a:
+ *   llk = lgamma(r + x) - lgamma(r) - lgamma(1 + x) - r softplus(l) - x softplus(-l)
+ *   zinb: t1 = llk - pi, t2 = softplus(-pi); log p = t1 - t2 where x > 1e-8, softplus(t1) - t2 otherwise
+ * dparams [B, P G] = -scale[0] * d log p / d params, the same planes.  lgamma(r + x) - lgamma(r) and psi(r + x) -
+ * psi(r) are formed as differences (exactly 0 at x = 0), in float64 inside the element.
+ * Contract of odin_elbo_cbernoulli_fwd_bwd: llk_part[b][part] in the layout odin_elbo_finalize / odin_sum_parts read,
+ * n_part = ceil(G / 256) (the shape alone), a NULL params pointer is a dry run that reports n_part, dparams_amax
+ * (optional) receives max |dparams| -- NOT bounded by scale[0] here -- fixed-order reductions (equal bits on every
+ * launch), every output written once.
+ * Domain: |a| <= 30 is tested and nothing is promised beyond a = 80.  Inside the float64 element nothing overflows
+ * there (e^a does near a = 709); what does is the float32 OUTPUT: past a = 88 r = e^a exceeds the float32 range, and with
+ * it r softplus(l) and r sigmoid(l) unless l is correspondingly negative -- where the reference's float32 e^a overflows
+ * itself.  x >= 0 need not be an integer.
+ * -2, nothing launched, no output touched: B < 1, G < 1 or > 2^28, zero_inflated outside {0, 1}, more than 2^31 - 1
+ * partials. */
+int odin_elbo_nb_fwd_bwd(const float* params, const float* x, float* llk_part, float* dparams, const float* scale,
+                         int B, int G, int zero_inflated, int* n_part_out, uint32_t* dparams_amax, void* stream);
+/* LogNorm (odin/networks/image_networks.py:138-151), the encoder's first layer of the gene-expression stacks:
+ * y[b, g] = log1p(1e4 x[b, g] / (sum_g x[b, g] + 1e-8)), one workgroup per row, the row total summed in float64 in a
+ * fixed order, the argument scaled in float64 and the logarithm taken in float32; a row of zeros gives zeros.  No
+ * parameters, no gradient.  y_amax (optional) receives max |y|, the activation range word of y.  -2: B < 1, G < 1 or
+ * G > 2^28. */
+int odin_lognorm_fwd(const float* x, float* y, int B, int G, uint32_t* y_amax, void* stream);
 /* Independent(Normal(loc, scale)) with params = split(h,2,axis=-1)
  * (image_networks.py:95-102): softplus1 = 1 -> scale = softplus(raw + softplus^-1(1))
  * (GaussianLayer, odin/bay/layers/continuous.py:196-260; odin/backend/maths.py:279-281);

@@ -121,6 +121,8 @@ SIGNATURES = {
     'odin_elbo_bernoulli_fwd_bwd': [P, P, P, P, P, I, I, IP, P],
     'odin_elbo_bernoulli_fwd_bwd_ranged': [P, P, P, P, P, I, I, IP, P, P],
     'odin_elbo_cbernoulli_fwd_bwd': [P, P, P, P, P, I, I, IP, P, P],
+    'odin_elbo_nb_fwd_bwd': [P, P, P, P, P, I, I, I, IP, P, P],
+    'odin_lognorm_fwd': [P, P, I, I, P, P],
     'odin_elbo_gaussian_fwd_bwd': [P, P, P, P, P, I, I, I, I, IP, P],
     'odin_gaussian_tail_applicable': [DP, I],
     'odin_gaussian_tail_fwd_bwd': [P, P, P, P, P, P, P, P, P, IP, P, IP, P, DP, I, I, P],

@@ -65,7 +65,9 @@ def build_layers(net: str, layers: Sequence[tuple], in_shape: Tuple[int, ...],
                  layout: ParamLayout) -> Tuple[List[LayerRec], Tuple[int, ...]]:
   """Resolve shapes / SAME pads and register parameters.  Returns (records, out_shape).
   Layer tuples: ('center',) ('conv',co,k,s,act) ('deconv',co,k,s,act) ('flatten',)
-  ('dense',units,act) ('reshape',(h,w,c)) -- cf. odin/networks/image_networks.py."""
+  ('dense',units,act) ('reshape',(h,w,c)) -- cf. odin/networks/image_networks.py.  ('lognorm',) (LogNorm,
+  image_networks.py:138-151) carries no parameters and is allowed only as the first layer of an encoder over flat
+  inputs: the engine issues odin_lognorm_fwd ahead of the encoder, the records start at the layer above it."""
   recs: List[LayerRec] = []
   shp = tuple(in_shape)
   center = False
@@ -73,6 +75,10 @@ def build_layers(net: str, layers: Sequence[tuple], in_shape: Tuple[int, ...],
     kind = L[0]
     if kind == 'center':
       center = True
+      continue
+    if kind == 'lognorm':
+      if net != 'enc' or li != 0 or len(shp) != 1:
+        raise ValueError("('lognorm',) is allowed only as the first layer of an encoder over flat inputs")
       continue
     if kind == 'flatten':
       shp = (int(np.prod(shp)),)
@@ -468,6 +474,7 @@ class NetProgram:
 # --------------------------------------------------------------------------------------
 # `softplus1` argument of odin_elbo_gaussian_fwd_bwd per two-parameter observation
 OBS_MODE = {'gaussian': 0, 'gaussian_softplus1': 1, 'qlogistic': 2}
+COUNT_OBS = {'nb': 2, 'zinb': 3}   # parameter planes of the count observations (elbo_counts.hip)
 MIXQL_K = 10  # components of the 'mixqlogistic' observation (image_networks.py:48)
 
 
@@ -475,6 +482,8 @@ def observation_maps(observation: str, C: int) -> int:
   """parameter maps the decoder emits per pixel for an observation over C channels."""
   if observation in ('bernoulli', 'cbernoulli'):
     return C
+  if observation in COUNT_OBS:   # C genes: the planes (a | l) or (a | l | pi)
+    return COUNT_OBS[observation] * C
   if observation == 'mixqlogistic':
     return MIXQL_K * (2 * C + C * (C - 1) // 2 + 1)
   return 2 * C
@@ -501,7 +510,8 @@ class LatentTerm(NamedTuple):
 class VAEEngine:
   """encoder -> q(z|x) -> decoder -> ELBO -> backward -> Adam for a FIXED batch size.
 
-  observation: 'bernoulli' | 'cbernoulli' | 'gaussian' | 'gaussian_softplus1' | 'qlogistic' | 'mixqlogistic'
+  observation: 'bernoulli' | 'cbernoulli' | 'gaussian' | 'gaussian_softplus1' | 'qlogistic' | 'mixqlogistic' |
+               'nb' | 'zinb' (counts over in_shape = (G,): the decoder emits the planes (a | l) / (a | l | pi))
   tc: None | 'betatc' (total_correlation, weight (beta-1))
   latent_reg: None | 'mmd' | 'dip_i' | 'dip_ii' (InfoVAE's maximum-mean discrepancy / DIPVAE's penalty, weight reg_coef)
   """
@@ -605,6 +615,10 @@ class VAEEngine:
     # KL form handed to the latent kernels: 0 = Monte-Carlo, 1 = closed-form KL(q||p),
     # 2 = closed-form KL(p||q) (`reverse=False`, odin/bay/helpers.py:261-265)
     self.observation = observation
+    if observation in COUNT_OBS and len(self.in_shape) != 1:
+      raise ValueError(f'observation={observation!r} takes flat count vectors: in_shape={self.in_shape}')
+    # LogNorm ahead of the encoder (the gene-expression stacks): the encoder reads x_ln, the observation the raw counts
+    self.lognorm = len(enc_layers) > 0 and enc_layers[0][0] == 'lognorm'
     if latent_cov not in ('diag', 'tril'):
       raise ValueError(f"latent_cov={latent_cov!r}: expected 'diag' or 'tril'")
     self.latent_cov = latent_cov
@@ -720,7 +734,8 @@ class VAEEngine:
     # a-priori bound 1 / B as a static word instead; that bound holds only for targets in [0, 1], and the reference's
     # Bernoulli takes any real target: a target of 6 overflowed the planes to inf.)
     # (the continuous Bernoulli's kernel does the same: dlogits = (mu(l) - x) / B_global)
-    self._bern_keeps_top = observation in ('bernoulli', 'cbernoulli') and bool(static_top_word)
+    # (and the count observations' kernel: max |dparams|, which 1 / B does not bound)
+    self._bern_keeps_top = (observation in ('bernoulli', 'cbernoulli') or observation in COUNT_OBS) and bool(static_top_word)
     if self._bern_keeps_top:
       self.dec.set_top_word(True)
     self.p = torch.empty(B, self.pw, **f32)
@@ -731,6 +746,7 @@ class VAEEngine:
     self.kl = torch.empty(B, **f32)
     self.fbmask = torch.empty(B, **f32)
     self.dh_e = torch.empty(B, self.hdim, **f32)
+    self.x_ln = torch.empty((B,) + self.in_shape, **f32) if self.lognorm else None
     n_per = int(np.prod(self.in_shape))
     self.n_per = n_per
     # per-sample partial log-likelihoods: the kernel reports how many it writes per sample
@@ -928,6 +944,8 @@ class VAEEngine:
 
   def _check_vamprior(self, analytic, reverse, free_bits, tc, latent_reg, capacity, range_words):
     K = self.vamp_K
+    if self.observation in COUNT_OBS or self.lognorm:
+      raise ValueError('vamprior_components with a count observation: the pseudo-inputs are clipped to [0, 1]')
     if not 1 <= K <= 1024:
       raise ValueError(f'vamprior_components={K}: the mixture kernel takes 1 .. 1024 components')
     if not 1 <= self.B <= 4096 or not 1 <= self.D <= 64:
@@ -1733,6 +1751,7 @@ class VAEEngine:
     counts no code usage, the neck stops behind the latent block and leaves the decoder's activation word alone; the
     decoder layers the fused launches evaluate as well land in dec.outs[0 / 1], unused."""
     lib, B, D = self.lib, self.B, self.D
+    x = self._encoder_input(x, st)
     if self.vq_K is not None:
       self._vq_assign(self.enc.forward(x, st), st, count=for_step)
       return self.z, 0
@@ -1783,6 +1802,15 @@ class VAEEngine:
                         self.free_bits, cap, st)
     return self.z, 0
 
+  def _encoder_input(self, x, st):
+    """what the encoder's first trainable layer reads (forward and weight gradient): x, or LogNorm(x) -- one launch ahead
+    of the encoder"""
+    if self.lognorm:
+      self.lib.odin_lognorm_fwd(x.data_ptr(), self.x_ln.data_ptr(), self.B, self.n_per, None, st)
+      x = self.x_ln
+    self.enc_x = x
+    return x
+
   def run_decoder(self, z: torch.Tensor, st=None):
     st = self.stream() if st is None else st
     assert z.shape == (self.B, self.D) and z.is_contiguous()
@@ -1815,6 +1843,9 @@ class VAEEngine:
       lib.odin_elbo_bernoulli_fwd_bwd_ranged(h_d, x, part, dlogits, inv_b, B, self.n_per, C.byref(npart), top_word, st)
     elif self.observation == 'cbernoulli':
       lib.odin_elbo_cbernoulli_fwd_bwd(h_d, x, part, dlogits, inv_b, B, self.n_per, C.byref(npart), top_word, st)
+    elif self.observation in COUNT_OBS:
+      lib.odin_elbo_nb_fwd_bwd(h_d, x, part, dlogits, inv_b, B, self.n_per, COUNT_OBS[self.observation] - 2,
+                               C.byref(npart), top_word, st)
     elif self.observation == 'mixqlogistic':
       lib.odin_elbo_mixqlogistic_fwd_bwd(h_d, x, part, dlogits, inv_b, B, self.n_per // Cc, Cc, MIXQL_K,
                                          C.byref(npart), st)
@@ -2111,7 +2142,7 @@ class VAEEngine:
     elif self._bwd_neck():
       ne = len(self.enc_recs)
       self._neck_bwd(dzx, tl, ts, st, jobs)
-      jobs += self.enc.backward(self.x, self.enc.gouts[ne - 3], st, fork=fork, last=ne - 3,
+      jobs += self.enc.backward(self.enc_x, self.enc.gouts[ne - 3], st, fork=fork, last=ne - 3,
                                 fuse_first=self._fuse_first_now())
     elif self._bwd_block():
       r0 = self.dec_recs[0]
@@ -2166,7 +2197,7 @@ class VAEEngine:
       if bslab is not None:
         jobs.append(self._slab_job(bslab, last.b_off, rows.value))
     if not self._bwd_neck():
-      jobs += self.enc.backward(self.x, self.enc.gouts[-1], st, fork=fork, fuse_first=self._fuse_first_now())
+      jobs += self.enc.backward(self.enc_x, self.enc.gouts[-1], st, fork=fork, fuse_first=self._fuse_first_now())
     if self.vamp_K is not None:
       self._backward_pseudo(st, jobs, late_jobs)
     jobs += late_jobs

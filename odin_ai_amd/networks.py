@@ -7,10 +7,12 @@ supervised / hierarchical arguments, same returned dictionary keys
 (``encoder, decoder, observation, latents``).
 
 Layer tuples: ('center',) | ('conv', filters, k, stride, act) | ('deconv', ...) |
-('flatten',) | ('dense', units, act) | ('reshape', (h, w, c)).
+('flatten',) | ('dense', units, act) | ('reshape', (h, w, c)) | ('lognorm',) (LogNorm, the first layer of the
+gene-expression encoders: no parameters).
 """
 from __future__ import annotations
 
+import re
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Sequence, Tuple
 
@@ -67,7 +69,10 @@ class RVconf:
 
 
 _OBS_PARAMS = {'bernoulli': 1, 'cbernoulli': 1, 'gaussian': 2, 'gaus': 2, 'normal': 2, 'gaussian_softplus1': 2,
-               'qlogistic': 2, 'mixqlogistic': None}
+               'qlogistic': 2, 'mixqlogistic': None, 'nb': 2, 'negativebinomial': 2, 'zinb': 3}
+# the rest of the count family of distribution_alias.py: refused, with a message that says so
+_COUNT_REFUSED = re.compile(r'^(nbshare|nbsingle|nbfull|zinbshare|zinbsingle|zinbfull|nbd\w*|negativebinomialdisp|zinbd\w*|'
+                            r'mixnb\w*|mnb|mixmass|mixzinb\w*|pois|poisson|zip\w*|zeroinflatedpoisson)$')
 
 
 def mixqlogistic_params_size(n_components: int, n_channels: int) -> int:
@@ -87,11 +92,20 @@ def _observation(input_shape, distribution: str, n_components: int = 10) -> Tupl
   model."""
   distribution = str(distribution).lower()
   if distribution not in _OBS_PARAMS:
+    more = ''
+    if _COUNT_REFUSED.match(distribution):
+      more = ("; of the count family only 'nb' / 'negativebinomial' and 'zinb' with full dispersion are built: shared "
+              "and single dispersion variables, the NegativeBinomialDisp, mixture and Poisson layers stay refused")
     raise ValueError(
         f"observation {distribution!r} is outside this build's scope "
-        f"(supported: bernoulli, cbernoulli, gaussian, gaussian_softplus1, qlogistic, mixqlogistic)")
-  name = {'gaus': 'gaussian', 'normal': 'gaussian'}.get(distribution, distribution)
+        f"(supported: bernoulli, cbernoulli, gaussian, gaussian_softplus1, qlogistic, mixqlogistic, nb, zinb{more})")
+  name = {'gaus': 'gaussian', 'normal': 'gaussian', 'negativebinomial': 'nb'}.get(distribution, distribution)
   C = int(input_shape[-1])
+  if name in ('nb', 'zinb'):
+    # (the planes (a | l) / (a | l | pi) = split(params, P, axis=-1) of a flat gene vector; observations.name 'mrna')
+    if len(tuple(input_shape)) != 1:
+      raise ValueError(f'observation {name!r} takes a flat count vector: input_shape={tuple(input_shape)}')
+    return C * _OBS_PARAMS[name], RVconf(tuple(input_shape), name, projection=True, name='mrna')
   if distribution == 'mixqlogistic':
     if C not in (1, 3) or int(n_components) != 10:
       raise ValueError('mixqlogistic: 1 or 3 channels, 10 components (the HIP kernel instances)')
@@ -249,7 +263,49 @@ def speech_networks(qz='mvndiag', zdim=None, activation='elu', n_frames: int = 9
               latents=RVconf((zdim,), qz, projection=True, name='Latents'))
 
 
+def _gene_networks(what, n_genes, distribution, zdim_default, qz, zdim, activation, is_semi_supervised,
+                   is_hierarchical, log_norm, cnn, units):
+  """the dense gene-expression stacks shared by cortex_networks / pbmc_networks (image_networks.py:732-896): LogNorm ->
+  Dense(u, activation) per unit | Dense(u, activation) per unit -> the observation's Dense projection (RVconf(...,
+  projection=True), the decoder's last layer here as in dense_networks)"""
+  if is_hierarchical or is_semi_supervised:
+    raise NotImplementedError('hierarchical / semi-supervised stacks are out of scope (SURVEY 8)')
+  if cnn:
+    raise NotImplementedError(f'{what}(cnn=True): the Conv1D / Conv1DTranspose stacks are not built (the engine\'s '
+                              f'convolutions are square); pass cnn=False for the Dense stacks')
+  if zdim is None:
+    zdim = zdim_default
+  if not isinstance(activation, str):
+    raise ValueError(f'{what}: activation={activation!r} must be a name (elu | relu | linear)')
+  input_shape = (int(n_genes),)
+  n_params, observation = _observation(input_shape, distribution)
+  units = tuple(int(u) for u in units)
+  enc = ([('lognorm',)] if log_norm else []) + [('dense', u, activation) for u in units]
+  dec = [('dense', u, activation) for u in units] + [('dense', n_params, 'linear')]
+  enc_names = [f'encoder{i}' for i in range(len(units))]
+  dec_names = [f'decoder{i}' for i in range(len(units))] + [observation.name]
+  return dict(encoder=SequentialNetwork(enc, 'encoder', input_shape, enc_names),
+              decoder=SequentialNetwork(dec, 'decoder', (zdim,), dec_names), observation=observation,
+              latents=RVconf((zdim,), qz, projection=True, name='latents'))
+
+
+def cortex_networks(qz='mvndiag', zdim=10, activation='elu', is_semi_supervised=False, is_hierarchical=False,
+                    log_norm=True, cnn=False, units=(256, 256, 256), **kwargs):
+  """image_networks.py:732-811: the Cortex mRNA stack, 558 genes under a negative-binomial ('nb') observation."""
+  return _gene_networks('cortex_networks', 558, 'nb', 10, qz, zdim, activation, is_semi_supervised, is_hierarchical,
+                        log_norm, cnn, units)
+
+
+def pbmc_networks(qz='mvndiag', zdim=32, activation='elu', is_semi_supervised=False, is_hierarchical=False,
+                  log_norm=True, cnn=True, units=(512, 512, 512), **kwargs):
+  """image_networks.py:814-896: the PBMC mRNA stack, 2019 genes under a zero-inflated negative-binomial ('zinb')
+  observation.  `cnn` defaults to True as in the reference, and the Conv1D stacks are not built: pass cnn=False."""
+  return _gene_networks('pbmc_networks', 2019, 'zinb', 32, qz, zdim, activation, is_semi_supervised, is_hierarchical,
+                        log_norm, cnn, units)
+
+
 _DATASETS = {
+    'cortex': cortex_networks, 'pbmc': pbmc_networks,
     'mnist': mnist_networks, 'binarizedmnist': mnist_networks, 'fashionmnist': mnist_networks,
     'dsprites': dsprites_networks, 'dspritesc': dsprites_networks,
     'shapes3d': shapes3d_networks, 'shapes3dsmall': shapes3d_networks,

@@ -454,6 +454,63 @@ class ContinuousBernoulliObservation:
     return torch.where(flat, u, y).clamp(0.0, 1.0)
 
 
+class NegativeBinomialObservation:
+  """Independent(NegativeBinomial(total_count = exp(a), logits = l), 1) ('nb'; NegativeBinomialLayer with dispersion
+  'full', odin/bay/layers/count_layers.py:75-163) over G genes: params [..., 2 G] = (a | l) = split(params, 2, axis=-1).
+  `log_prob` runs the HIP kernel of the training step (odin_elbo_nb_fwd_bwd): lgamma(r + x) - lgamma(r) is
+  formed as a difference there, which torch.lgamma in float32 cannot do."""
+  PLANES = 2
+
+  def __init__(self, params: torch.Tensor, lib=None):
+    assert params.shape[-1] % self.PLANES == 0, params.shape
+    self.params, self._lib = params, lib
+    G = params.shape[-1] // self.PLANES
+    self.log_total_count, self.logits = params[..., :G], params[..., G:2 * G]
+
+  event_shape = property(lambda self: tuple(self.logits.shape[1:]))
+  batch_shape = property(lambda self: (self.logits.shape[0],))
+  total_count = property(lambda self: torch.exp(self.log_total_count))
+
+  def mean(self):
+    return torch.exp(self.log_total_count + self.logits)
+
+  def log_prob(self, x):
+    lib = self._lib if self._lib is not None else _lib.load()
+    P, G = self.PLANES, self.logits.shape[-1]
+    p = self.params.reshape(-1, P * G).to(torch.float32).contiguous()
+    rows = p.shape[0]
+    xx = torch.as_tensor(x, dtype=torch.float32, device=p.device).expand(self.logits.shape).reshape(rows, G).contiguous()
+    st = torch.cuda.current_stream(p.device).cuda_stream if p.device.type == 'cuda' else None
+    npart = C.c_int(0)
+    lib.odin_elbo_nb_fwd_bwd(None, None, None, None, None, rows, G, P - 2, C.byref(npart), None, None)
+    part, dp = torch.empty(rows * npart.value, dtype=torch.float32, device=p.device), torch.empty_like(p)
+    out, one = torch.empty(rows, dtype=torch.float32, device=p.device), torch.ones(1, dtype=torch.float32, device=p.device)
+    lib.odin_elbo_nb_fwd_bwd(p.data_ptr(), xx.data_ptr(), part.data_ptr(), dp.data_ptr(), one.data_ptr(), rows, G, P - 2,
+                             C.byref(npart), None, st)
+    lib.odin_sum_parts(part.data_ptr(), npart.value, out.data_ptr(), rows, st)
+    return out.reshape(self.logits.shape[:-1])
+
+  def sample(self, n=None):
+    raise NotImplementedError(f'{type(self).__name__}.sample: sampling the count observations is not built')
+
+
+class ZINegativeBinomialObservation(NegativeBinomialObservation):
+  """ZeroInflated(NegativeBinomial(exp(a), logits = l), logits = pi) ('zinb'; ZINegativeBinomialLayer,
+  count_layers.py:311-416; zero_inflated.py:216-230): params [..., 3 G] = (a | l | pi), pi the inflation logit; `rate` is
+  the inflation probability sigmoid(pi)."""
+  PLANES = 3
+
+  def __init__(self, params: torch.Tensor, lib=None):
+    super().__init__(params, lib)
+    G = params.shape[-1] // 3
+    self.inflation_logits = params[..., 2 * G:]
+
+  rate = property(lambda self: torch.sigmoid(self.inflation_logits))
+
+  def mean(self):
+    return torch.sigmoid(-self.inflation_logits) * super().mean()
+
+
 class GaussianObservation:
   """Independent(Normal(loc, scale), 3), params split on the channel axis
   (image_networks.py:95-102); softplus1 scale as GaussianLayer (continuous.py:196-260)."""
@@ -884,6 +941,10 @@ class VariationalAutoencoder:
       return BernoulliObservation(h)
     if self.observation.posterior == 'cbernoulli':
       return ContinuousBernoulliObservation(h)
+    if self.observation.posterior == 'nb':
+      return NegativeBinomialObservation(h, self._lib)
+    if self.observation.posterior == 'zinb':
+      return ZINegativeBinomialObservation(h, self._lib)
     if self.observation.posterior == 'qlogistic':
       return QuantizedLogisticObservation(h)
     if self.observation.posterior == 'mixqlogistic':
