@@ -921,6 +921,32 @@ int odin_skip_head_bwd(const float* x, const float* h, const float* w, const flo
                        uint32_t* dh_amax, float* dx, float* slab, int* slab_rows_out, int B, int Dx, int H, int N,
                        void* stream);
 
+/* ---- the semi-supervised label head of MultitaskVAE / SkiptaskVAE (label_head.hip; odin/bay/vi/autoencoder/
+ * multitask_vae.py:164-207): Dense(D -> K) giving the logits of a OneHotCategorical over a FRESH posterior sample, for the
+ * labelled rows [row0, row0 + Bs) of p [B, 2 D] = (loc | raw):
+ *   z' = loc + softplus(raw) eps_y;   l = z' w + bias   (w [D, K] row-major: a Dense kernel; bias may be NULL)
+ *   llk[b] = sum_k y_k (l_k - logsumexp(l))   (the maximum subtracted first; y [Bs, K] float, one-hot or soft)
+ *   g_k = y_k - softmax_k sum_j y_j,  dz' = w g,  and with c = coef[0] (a DEVICE scalar: graph replays see the schedule)
+ *   dloc [B, D] = c dz',  dscale [B, D] = c dz' eps_y  -- the gradient inputs of odin_latent_bwd, in the convention of
+ *   odin_total_correlation_fwd_bwd (dscale is taken with respect to softplus(raw)); every row outside the labelled block
+ *   is written as zero on every launch.
+ *   value[0] = (1 / Bs) sum_b llk[b];  value[1] is the launch's ticket word: zero before the first launch, left zero.
+ *   logits [Bs, K] is optional (NULL).  eps_y [Bs, D], llk [Bs].
+ *   slab[g][D K | K]: per-workgroup partial (dW | db) = c (sum_b z'_b g_b^T | sum_b g_b), to be summed by
+ *   odin_slab_reduce -- *slab_rows_out rows, at most 32.  slab == NULL = dry run (the row count only).
+ * One wave per sample, one launch, no float atomics: every sum, the batch mean included, runs in a fixed order and two
+ * calls give the same bits.  Outputs are finite for logits of magnitude 1e4 and raw scales in [-80, 80]; an all-zero row
+ * of y gives llk = 0 and zero gradients.
+ * Limits: 1 <= D <= 255, 1 <= K <= 255, 1 <= Bs, 0 <= row0, row0 + Bs <= B; anything else, and a call with a slab but a
+ * NULL operand, returns -2, launches nothing and touches no output (*slab_rows_out included). */
+int odin_label_head_fwd_bwd(const float* p, const float* eps_y, const float* w, const float* bias, const float* y,
+                            const float* coef, float* logits, float* llk, float* value, float* dloc, float* dscale,
+                            float* slab, int* slab_rows_out, int B, int row0, int Bs, int D, int K, void* stream);
+/* The forward half from a given z [n, D]: logits [n, K] = z w + bias, in the summation order of the fused launch
+ * (MultitaskVAE.predict_labels).  Limits: 1 <= D, K <= 255, 1 <= n. */
+int odin_label_head_fwd(const float* z, const float* w, const float* bias, float* logits, int n, int D, int K,
+                        void* stream);
+
 /* ---- HIP-graph helpers (capture a sequence of the calls above, replay per step) ------- */
 int odin_graph_begin(void* stream);
 int odin_graph_end(void* stream, void** graph_exec_out);

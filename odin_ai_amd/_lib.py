@@ -131,6 +131,8 @@ SIGNATURES = {
     'odin_disc_head_fwd_bwd': [P, P, P, P, I, P, P, P, I, P, P, P, IP, P, I, I, P],
     'odin_skip_head_fwd': [P, P, P, P, P, I, P, P, P, P, I, I, I, I, P],
     'odin_skip_head_bwd': [P, P, P, P, I, P, P, P, P, IP, I, I, I, I, P],
+    'odin_label_head_fwd_bwd': [P, P, P, P, P, P, P, P, P, P, P, P, IP, I, I, I, I, I, P],
+    'odin_label_head_fwd': [P, P, P, P, I, I, I, P],
     'odin_debug_igemm_h_min_flop': [C.c_double],
     'odin_debug_blk_min_flop': [C.c_double],
     'odin_debug_blk_planes': [C.c_int],

@@ -492,11 +492,12 @@ H_CAP = 15  # BetaCapacityVAE: the capacity C(step) (slots 10..14: the second op
 N_HYPER = 16
 MMD_KERNELS = {'gaussian': 0, 'linear': 1}   # odin_mmd_fwd_bwd's `kernel`
 PRIOR_KEY_SALT = 0x6D6D6470 << 32            # high word of the prior stream's Philox key (eps streams: seed < 2^32)
+LABEL_KEY_SALT = 0x6C61626C << 32            # the same for the label head's noise eps_y (label_head.hip)
 
 
 class LatentTerm(NamedTuple):
   """The ONE term a step adds to the loss beside log-likelihood and KL, resolved at planning time (_plan_term): beta-TC,
-  MMD, DIP, VampPrior's c, the quantiser's commitment -- or none."""
+  MMD, DIP, VampPrior's c, the quantiser's commitment, the label likelihood of a labelled step -- or none."""
   value: Optional[torch.Tensor] = None    # its first float is what odin_elbo_finalize scales by H_TCCOEF
   dz: Optional[torch.Tensor] = None       # the three gradient inputs of the latent backward
   dloc: Optional[torch.Tensor] = None
@@ -533,7 +534,7 @@ class VAEEngine:
                vq_codes: Optional[int] = None, vq_code_size: Optional[int] = None, vq_commitment: float = 0.25,
                vq_ema: bool = False, vq_ema_decay: float = 0.99, vq_epsilon: float = 1e-5, vq_state=None,
                latent_cov: str = 'diag', chain_fwd: bool = True, latent_dist: str = 'normal',
-               temperature: float = 0.5):
+               temperature: float = 0.5, label_units: Optional[int] = None):
     """The keyword-only arguments are the engine's launch-order / A-B options (tests and tools pass them; the engine
     reads no environment variable):
       act_words        activation range words for the two-plane consumers; False: unscaled planes
@@ -605,7 +606,16 @@ class VAEEngine:
     same unfused slot; 1 <= zdim <= 255):
       latent_dist     'relaxedbernoulli': q(z|x) = RelaxedBernoulli(temperature, logits), zdim INDEPENDENT binary units;
                       the projection is hdim -> zdim (the logits), `eps` holds the logistic noise (train_step's `eps`
-                      argument is that noise; None: drawn inside the forward kernel)"""
+                      argument is that noise; None: drawn inside the forward kernel)
+    The semi-supervised label head of MultitaskVAE / SkiptaskVAE (label_head.hip; excludes every other term
+    -- tc, latent_reg, vamprior_components, vq_codes --, every posterior but the diagonal Gaussian, and data parallelism):
+      label_units     None | K: Dense(zdim -> K) on a fresh posterior sample gives the logits of a OneHotCategorical; its
+                      kernel and bias are the LAST entries of the parameter layout (keys ('lab', 'w') / ('lab', 'b')).  A
+                      step is labelled when set_labels / train_step(labels=) hands it y [B / 2, K]: the batch is then
+                      cat(x_u, x_s), the labelled rows are [B / 2, B), the hyper row carries 2 / B and 2 beta / B (the
+                      reference adds the two half-batch means) and the term -alpha * mean_s log p(y | z') joins the loss
+                      (out4[3]; label_step_outputs() gives the reference's loss and five metrics).  An unlabelled step
+                      issues the launches of an engine without labels and hands W, b a zero gradient."""
     self.lib = lib if lib is not None else _lib.load()
     self.device = torch.device(device)
     self.B, self.D = int(batch_size), int(zdim)
@@ -656,6 +666,10 @@ class VAEEngine:
       self._check_concrete(tc, latent_reg, vamprior_components, vq_codes, range_words, neck_bwd)
     if latent_dist == 'relaxedbernoulli':
       self._check_relaxedbern(tc, latent_reg, vamprior_components, vq_codes, range_words, neck_bwd)
+    self.label_K = None if label_units is None else int(label_units)
+    self._labelled = False
+    if self.label_K is not None:
+      self._check_labels(tc, latent_reg, vamprior_components, vq_codes)
     # width of the latent projection: (loc | raw scale), (loc | the D (D + 1) / 2 raw entries of L) or the logits
     self.pw = self.D + self.D * (self.D + 1) // 2 if latent_cov == 'tril' else 2 * self.D
     if latent_dist in ('relaxedonehot', 'relaxedbernoulli'):
@@ -683,6 +697,11 @@ class VAEEngine:
       # the pseudo-inputs: one more parameter tensor behind the networks', so that gradients, Adam moments, the norm,
       # the NaN guard and the checkpoint code see it like any other
       self.vamp_u_off = self.layout.add(('vamp', 'u'), (self.vamp_K, int(np.prod(self.in_shape))))
+    if self.label_K is not None:
+      # the label head's Dense(D -> K): behind every other parameter (a model with labels starts from the same bits as
+      # one without), (W | b) contiguous like a layer's: gradients, Adam, the policies and checkpoints cover them
+      self.lab_w_off = self.layout.add(('lab', 'w'), (self.D, self.label_K))
+      self.lab_b_off = self.layout.add(('lab', 'b'), (self.label_K,))
     self.layout.pad_to(4)
     self.out_shape = do
     C_in = self.in_shape[-1]
@@ -798,6 +817,8 @@ class VAEEngine:
       self._plan_vq(f32, own_params, vq_state)
     if self.vamp_K is not None:
       self._plan_vamprior(f32, mr, act_words, small_wgrad_gf)
+    if self.label_K is not None:
+      self._plan_labels(f32)
     self._term = self._plan_term()
     self.ws = torch.empty(4096, **f32)
     self.gnorm2 = torch.zeros(1, **f32)
@@ -904,7 +925,104 @@ class VAEEngine:
       return LatentTerm(self.vamp_ws, dz=self.vamp_dz, launch=self._vamp_term)
     if self.vq_K is not None:
       return LatentTerm(self.out8[4:])   # m, left by the quantiser (its gradient is formed inside odin_vq_bwd)
+    if self.label_K is not None:
+      return LatentTerm(self.lab_value, dloc=self.lab_dloc, dscale=self.lab_dscale, launch=self._label_term)
     return LatentTerm()
+
+  @property
+  def _step_term(self) -> LatentTerm:
+    """the term of THIS step: the label likelihood is on for a labelled step only"""
+    if self.label_K is not None and not self._labelled:
+      return LatentTerm()
+    return self._term
+
+  # ---- semi-supervised label head (label_head.hip; DESIGN 3.21) ---------------------------------------------------------
+  def _check_labels(self, tc, latent_reg, vamprior_components, vq_codes):
+    who = 'label_units'
+    if not 1 <= self.label_K <= 255:
+      raise ValueError(f'{who}={self.label_K} outside the kernel (1 .. 255: four classes per lane)')
+    if self.latent_cov == 'tril' or self.latent_dist != 'normal':
+      raise NotImplementedError(f"{who} needs the 'mvndiag' posterior: the fresh sample z' = loc + softplus(raw) eps_y is "
+                                f'written for it')
+    if not 1 <= self.D <= 255:
+      raise ValueError(f'{who}: zdim={self.D} outside the kernel (1 .. 255)')
+    self._check_no_term(who, 'a step carries one term beside log-likelihood and KL', tc, latent_reg)
+    if vamprior_components is not None:
+      raise ValueError(f'{who} cannot be combined with vamprior_components (a step carries one term)')
+    if vq_codes is not None:
+      raise ValueError(f'{who} cannot be combined with vq_codes (there is no Gaussian posterior)')
+    if self.is_dp:
+      raise NotImplementedError(f'{who} under data parallelism (world_size > 1 / force_dp) is not offered')
+
+  def _plan_labels(self, f32):
+    B, D, K = self.B, self.D, self.label_K
+    self.lab_Bs = max(B // 2, 1)
+    rows = C.c_int(0)
+    self.lib.odin_label_head_fwd_bwd(None, None, None, None, None, None, None, None, None, None, None, None,
+                                     C.byref(rows), max(B, 2), max(B, 2) - self.lab_Bs, self.lab_Bs, D, K, None)
+    self.lab_rows = rows.value
+    self.lab_slab = torch.empty(rows.value, D * K + K, **f32)
+    self.lab_eps = torch.zeros(self.lab_Bs, D, **f32)
+    self.lab_y = torch.zeros(self.lab_Bs, K, **f32)
+    self.lab_logits = torch.empty(self.lab_Bs, K, **f32)
+    self.lab_llk = torch.zeros(self.lab_Bs, **f32)
+    self.lab_value = torch.zeros(2, **f32)   # (the mean | the launch's ticket word)
+    self.lab_dloc = torch.zeros(B, D, **f32)
+    self.lab_dscale = torch.zeros(B, D, **f32)
+    self.label_key = (self.seed ^ LABEL_KEY_SALT) & 0xFFFFFFFFFFFFFFFF
+    self._eps_y_explicit = False
+
+  def set_labels(self, y: Optional[torch.Tensor], eps_y: Optional[torch.Tensor] = None) -> None:
+    """y [B / 2, K] (float; one-hot or soft): the next forward / train_step is a labelled step over cat(x_u, x_s);
+    None: an unlabelled one.  `eps_y` [B / 2, D]: the fresh sample's noise (None: drawn from (seed, step) on the device)."""
+    assert self.label_K is not None, 'this engine was built without label_units'
+    self._labelled = y is not None
+    if y is None:
+      assert eps_y is None
+      return
+    if self.B % 2 != 0:
+      raise ValueError(f'a labelled step splits the batch in two equal halves: batch_size={self.B} is odd')
+    if tuple(y.shape) != tuple(self.lab_y.shape):
+      raise ValueError(f'labels: expected {tuple(self.lab_y.shape)}, got {tuple(y.shape)}')
+    if y.data_ptr() != self.lab_y.data_ptr():
+      self.lab_y.copy_(y, non_blocking=True)
+    self._eps_y_explicit = eps_y is not None
+    if eps_y is not None and eps_y.data_ptr() != self.lab_eps.data_ptr():
+      self.lab_eps.copy_(eps_y.reshape(self.lab_eps.shape), non_blocking=True)
+
+  def _label_term(self, st):
+    B, D, K, Bs = self.B, self.D, self.label_K, self.lab_Bs
+    if not self._eps_y_explicit:
+      self.lib.odin_rng_normal(self.lab_eps.data_ptr(), Bs * D, self.label_key, self.hp(N_HYPER), st)
+    rows = C.c_int(0)
+    self.lib.odin_label_head_fwd_bwd(self.p.data_ptr(), self.lab_eps.data_ptr(), self.params[self.lab_w_off:].data_ptr(),
+                                     self.params[self.lab_b_off:].data_ptr(), self.lab_y.data_ptr(), self.hp(H_TCGRAD),
+                                     self.lab_logits.data_ptr(), self.lab_llk.data_ptr(), self.lab_value.data_ptr(),
+                                     self.lab_dloc.data_ptr(), self.lab_dscale.data_ptr(), self.lab_slab.data_ptr(),
+                                     C.byref(rows), B, B - Bs, Bs, D, K, st)
+    assert rows.value == self.lab_rows
+
+  def label_logits(self, z: torch.Tensor, out: Optional[torch.Tensor] = None, st=None) -> torch.Tensor:
+    """logits [n, K] of the label head at given codes z [n, D] (odin_label_head_fwd)"""
+    st = self.stream() if st is None else st
+    n = z.shape[0]
+    assert z.shape == (n, self.D) and z.is_contiguous()
+    out = torch.empty(n, self.label_K, dtype=torch.float32, device=self.device) if out is None else out
+    self.lib.odin_label_head_fwd(z.data_ptr(), self.params[self.lab_w_off:].data_ptr(),
+                                 self.params[self.lab_b_off:].data_ptr(), out.data_ptr(), n, self.D, self.label_K, st)
+    return out
+
+  def label_step_outputs(self, beta: float) -> Dict[str, torch.Tensor]:
+    """after a LABELLED forward / train_step: the reference's loss and metrics (multitask_vae.py:164-207) from the
+    per-sample llk / kl the step left -- loss = -mean_u(llk - beta kl) - mean_s(llk - beta kl) - alpha mean_s log p(y|z'),
+    the two half-batch means ADDED (out4 holds the joint-batch means: its loss is not the reference's)"""
+    h = self.B // 2
+    llk, kl = self.llk, self.kl
+    o = {'uns/llk': llk[:h].mean(), 'sup/llk': llk[h:].mean(), 'uns/kl': float(beta) * kl[:h].mean(),
+         'sup/kl': float(beta) * kl[h:].mean(), 'sup/llk_y': -self.out4[3]}
+    # (the reference's llk entry of the labels carries alpha: reduce_mean(alpha * llk_y), multitask_vae.py:194)
+    o['loss'] = -(o['uns/llk'] - o['uns/kl']) - (o['sup/llk'] - o['sup/kl']) - o['sup/llk_y']
+    return o
 
   def _tc_local(self, st):
     self.lib.odin_total_correlation_fwd_bwd(self.z.data_ptr(), self.p.data_ptr(), self.tc_ws.data_ptr(),
@@ -1605,16 +1723,22 @@ class VAEEngine:
   def set_hyper(self, lr=1e-3, beta=1.0, b1=0.9, b2=0.999, eps=1e-7, grad_scale=1.0,
                 t: Optional[int] = None, tc_coef: Optional[float] = None,
                 skip_enable: bool = True, extra: Optional[Sequence[float]] = None,
-                capacity: Optional[float] = None, reg_coef: Optional[float] = None):
-    """Host scalars -> device (one small async H2D copy)."""
+                capacity: Optional[float] = None, reg_coef: Optional[float] = None,
+                label_alpha: Optional[float] = None):
+    """Host scalars -> device (one small async H2D copy).  `label_alpha` (label_units): the weight of the label term of
+    a LABELLED step; None: an unlabelled step."""
     t = self.step_count if t is None else t
+    if self.label_K is not None and label_alpha is None:
+      # a row without the label term belongs to an unlabelled pass: a caller that never heard of labels (the base
+      # class's encode / elbo_components / evaluation step) must not launch the head on the labels of an earlier step
+      self._labelled = False
     self._ring_live = False   # (an explicit copy: whatever the ring predicted for this step no longer counts)
     self._ring_i = (self._ring_i + 1) % len(self._ring)
     h = self._ring[self._ring_i]
     if self._ring_ev[self._ring_i] is not None:
       self._ring_ev[self._ring_i].synchronize()
     self._fill_row(h, t, lr=lr, beta=beta, b1=b1, b2=b2, eps=eps, grad_scale=grad_scale, tc_coef=tc_coef,
-                   skip_enable=skip_enable, extra=extra, capacity=capacity, reg_coef=reg_coef)
+                   skip_enable=skip_enable, extra=extra, capacity=capacity, reg_coef=reg_coef, label_alpha=label_alpha)
     # (leaving this 80-byte copy out of the steady state was measured in round 4 at 0.72 ms per step: no difference;
     # at 0.52 ms it is worth 7-8 us -- profiles/r05_hyper_ring.txt -- hence the device ring of train_step)
     self.hyper.copy_(h, non_blocking=True)
@@ -1624,7 +1748,7 @@ class VAEEngine:
       self._ring_ev[self._ring_i] = ev
 
   def _fill_row(self, h, t, lr=1e-3, beta=1.0, b1=0.9, b2=0.999, eps=1e-7, grad_scale=1.0, tc_coef=None,
-                skip_enable=True, extra=None, capacity=None, reg_coef=None):
+                skip_enable=True, extra=None, capacity=None, reg_coef=None, label_alpha=None):
     """the hyper-parameter row of step t into the host tensor h (N_HYPER + 4 floats)"""
     tt = max(int(t), 1)
     Bg = self.B * self.world_size
@@ -1651,6 +1775,14 @@ class VAEEngine:
     if self.vq_K is not None:
       # VQVAE: the term (commitment weight (+ 1 for `latents`)) * m; its gradient is formed inside odin_vq_bwd
       h[H_TCCOEF] = self.vq_cw + (0.0 if self.vq_ema else 1.0)
+    if self.label_K is not None and label_alpha is not None:
+      # a labelled step over cat(x_u, x_s): the reference ADDS the means of the two halves (multitask_vae.py:185-207),
+      # twice the joint-batch mean -- every kernel that scales a gradient reads 1 / B or beta / B from this row; the label
+      # term is -alpha * mean_s llk_y, its gradient -alpha / B_s * d(sum_s llk_y)
+      h[H_INVB] = 2.0 / Bg
+      h[H_KLW] = 2.0 * beta / Bg
+      h[H_TCCOEF] = -float(label_alpha)
+      h[H_TCGRAD] = -float(label_alpha) / (self.B // 2)
     if extra is not None:  # second optimiser's Adam block (FactorVAE discriminator), slots 10..14
       for i, val in enumerate(extra):
         h[10 + i] = float(val)
@@ -1964,12 +2096,13 @@ class VAEEngine:
         self._dip_moments(st)
       self._llk_part_used = llk_part
       return h_d
-    if self._term.launch is not None:
-      self._term.launch(st)
+    term = self._step_term
+    if term.launch is not None:
+      term.launch(st)
     self._llk_part_used = llk_part
     if finalize:
       lib.odin_elbo_finalize(llk_part.data_ptr(), self.n_part, self.kl.data_ptr(), self.hp(H_BETA),
-                             self._term.ptr() if tc_ptr is None else tc_ptr, self.llk.data_ptr(), self.out4.data_ptr(),
+                             term.ptr() if tc_ptr is None else tc_ptr, self.llk.data_ptr(), self.out4.data_ptr(),
                              B, st)
     return h_d
 
@@ -2128,7 +2261,7 @@ class VAEEngine:
 
   def _backward_enc(self, st, extra_dz, fork, jobs, late_jobs):
     lib, B, D = self.lib, self.B, self.D
-    T = self._term
+    T = self._step_term
     # (the caller's dz -- FactorVAE's -- and the term's share one input of the latent backward; the quantiser has none)
     assert extra_dz is None or (T.dz is None and self.vq_K is None)
     dzx, tl, ts = (None if t is None else t.data_ptr()
@@ -2200,6 +2333,9 @@ class VAEEngine:
       jobs += self.enc.backward(self.enc_x, self.enc.gouts[-1], st, fork=fork, fuse_first=self._fuse_first_now())
     if self.vamp_K is not None:
       self._backward_pseudo(st, jobs, late_jobs)
+    if self.label_K is not None:
+      # (dW | db) of the label head; an unlabelled step reduces zero rows: the job writes zeros
+      jobs.append(self._slab_job(self.lab_slab, self.lab_w_off, self.lab_rows if self._labelled else 0))
     jobs += late_jobs
     # the range words of the gradient tensors (their producers fold in with atomicMax, so every step starts from
     # zero): cleared by the step's LAST backward launch -- a reduction over zero slab rows writes zeros -- instead
@@ -2385,7 +2521,7 @@ class VAEEngine:
       # update's first launch instead of being a launch of its own
       def fwd():
         self.forward(x, eps, finalize=False, prior=prior)
-        self._fin_pending = (self._llk_part_used.data_ptr(), self.n_part, self._term.ptr())
+        self._fin_pending = (self._llk_part_used.data_ptr(), self.n_part, self._step_term.ptr())
       P.append(('k', fwd))
     if self.is_dp and self.dp_buckets >= 2:
       cur = lambda: torch.cuda.current_stream(self.device)
@@ -2428,22 +2564,31 @@ class VAEEngine:
                  clipnorm: Optional[float] = None, clipvalue: Optional[float] = None,
                  skip_update_threshold: Optional[float] = None, when_skip_update: int = 0,
                  check_nan: bool = True, capacity: Optional[float] = None, schedule=None,
-                 prior: Optional[torch.Tensor] = None, reg_coef: Optional[float] = None):
+                 prior: Optional[torch.Tensor] = None, reg_coef: Optional[float] = None,
+                 labels: Optional[torch.Tensor] = None, eps_y: Optional[torch.Tensor] = None, label_alpha: float = 10.0):
     """Networks.optimize for one VAEStep: step += 1, forward, backward, (all-reduce), gradient
     policies, Adam.  Returns the device tensor out4 = [loss, mean llk, mean beta*kl, tc] (no host
     sync).  `prior` (latent_reg='mmd'): an explicit prior sample [M, D] for this step; `reg_coef`: the regulariser's
-    weight for this step (default: the constructor's)."""
+    weight for this step (default: the constructor's).  `labels` [B / 2, K] (label_units): a labelled step over
+    x = cat(x_u, x_s) with the term -label_alpha * mean_s log p(y | z'), `eps_y` [B / 2, D] its fresh sample's noise; then
+    out4[0] is the joint-batch form, label_step_outputs() the reference's loss."""
     self.step_count += 1
+    if self.label_K is not None:
+      self.set_labels(labels, eps_y)
+    else:
+      assert labels is None and eps_y is None, 'labels need an engine built with label_units'
     # the device ring serves the update path whose last two launches are odin_sumsq_adam_ring (norm + Adam)
     ring = bool(self.use_hyper_ring and clipvalue is None and (global_clipnorm is not None or check_nan))
     if ring:
       args = dict(lr=lr, beta=beta, when_skip_update=int(when_skip_update), capacity=capacity)
       if reg_coef is not None:
         args['reg_coef'] = reg_coef
+      if self.label_K is not None:
+        args['label_alpha'] = float(label_alpha) if self._labelled else None
       self._ring_step(self.step_count, args, schedule)
     else:
       self.set_hyper(lr=lr, beta=beta, skip_enable=self.step_count >= int(when_skip_update), capacity=capacity,
-                     reg_coef=reg_coef)
+                     reg_coef=reg_coef, label_alpha=label_alpha if self._labelled else None)
     pol = (global_clipnorm, clipnorm, clipvalue, skip_update_threshold, bool(check_nan), ring)
     if prior is not None:
       assert self.reg_mode == 'mmd', 'an explicit prior sample needs latent_reg="mmd"'
@@ -2480,6 +2625,8 @@ class VAEEngine:
     key = (pol, self.analytic, self.free_bits, eps is not None, self.dp_buckets)
     if prior is not None:   # (an explicit prior sample: a graph of its own that reads reg_y)
       key = key + ('prior',)
+    if self.label_K is not None:   # (a labelled step has launches of its own; lab_y / lab_eps are static buffers)
+      key = key + ('labelled', self._labelled, self._labelled and self._eps_y_explicit)
     if not hasattr(self, '_graphs'):
       self._graphs = {}
     if key not in self._graphs:

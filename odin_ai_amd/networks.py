@@ -48,7 +48,10 @@ class RVconf:
   needs: event shape, posterior alias, whether a Dense projection is added, name.  Posterior aliases of the latents
   (distribution_alias.py): 'mvndiag', 'mvntril', and 'relaxedonehot' / 'relaxedsoftmax' -- ONE event_shape[0]-way relaxed
   one-hot variable whose constant temperature is kwargs['temperature'] (default 0.5) -- and 'relaxedbern' /
-  'relaxedsigmoid' / 'relaxedbernoulli': event_shape[0] independent relaxed Bernoulli units at such a temperature."""
+  'relaxedsigmoid' / 'relaxedbernoulli': event_shape[0] independent relaxed Bernoulli units at such a temperature.
+  Posterior alias of a label variable (MultitaskVAE / SkiptaskVAE's `labels`): 'onehot' -- with projection=True a
+  Dense(zdim -> event_shape[0]) on the latent code gives the logits of a OneHotCategorical; `name` names its checkpoint
+  variables (<name>/kernel, <name>/bias) and its metric (sup/llk_<name>)."""
   event_shape: Tuple[int, ...]
   posterior: str = 'mvndiag'
   projection: bool = True
@@ -181,9 +184,11 @@ def celeba_networks(qz='mvndiag', zdim=None, activation='elu', is_semi_supervise
 def mnist_networks(qz='mvndiag', zdim=None, activation='elu', is_semi_supervised=False,
                    is_hierarchical=False, centerize_image=True, distribution='bernoulli',
                    n_channels=1, **kwargs):
-  """image_networks.py:223-292."""
-  if is_hierarchical or is_semi_supervised:
-    raise NotImplementedError('hierarchical / semi-supervised stacks are out of scope (SURVEY 8)')
+  """image_networks.py:223-292.  is_semi_supervised=True adds the `labels` entry of :285-291: the ten digit classes as
+  RVconf(10, 'onehot', projection=True), named kwargs['labels_name'] (default 'digits') -- the label head of
+  MultitaskVAE / SkiptaskVAE."""
+  if is_hierarchical:
+    raise NotImplementedError('hierarchical stacks are out of scope (SURVEY 8)')
   if zdim is None:
     zdim = 32
   input_shape = (28, 28, n_channels)
@@ -197,10 +202,13 @@ def mnist_networks(qz='mvndiag', zdim=None, activation='elu', is_semi_supervised
          ('conv', n_params, 1, 1, 'linear')]
   enc_names = ['encoder0', 'encoder1', 'encoder2', 'encoder3', 'encoder_proj']
   dec_names = ['decoder_proj', 'decoder2', 'decoder3', 'decoder4', 'decoder5', 'decoder6']
-  return dict(encoder=SequentialNetwork(enc, 'Encoder', input_shape, enc_names),
-              decoder=SequentialNetwork(dec, 'Decoder', (zdim,), dec_names),
-              observation=observation,
-              latents=RVconf((zdim,), qz, projection=True, name='latents'))
+  networks = dict(encoder=SequentialNetwork(enc, 'Encoder', input_shape, enc_names),
+                  decoder=SequentialNetwork(dec, 'Decoder', (zdim,), dec_names),
+                  observation=observation,
+                  latents=RVconf((zdim,), qz, projection=True, name='latents'))
+  if is_semi_supervised:
+    networks['labels'] = RVconf(10, 'onehot', projection=True, name=kwargs.get('labels_name', 'digits'))
+  return networks
 
 
 def dense_networks(input_shape=(28, 28, 1), zdim=16, units=(512, 512), activation='relu',

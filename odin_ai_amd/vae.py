@@ -10,6 +10,7 @@ arguments, method names, returned structures and error behaviour):
   odin/bay/vi/autoencoder/info_vae.py:28-91               (InfoVAE: maximum-mean discrepancy)
   odin/bay/vi/autoencoder/dip_vae.py                      (DIPVAE: disentangled inferred prior)
   odin/bay/vi/autoencoder/two_stage_vae.py                (TwoStageVAE: a second VAE over the latents)
+  odin/bay/vi/autoencoder/multitask_vae.py                (MultitaskVAE / SkiptaskVAE: a label head on the latents)
   odin/networks/base_networks.py:415-812                  (optimize(), fit())
   odin/bay/layers/continuous.py:459-483                   (latent posteriors 'mvndiag' and 'mvntril')
   odin/bay/layers/discrete.py:286-343                     (latent posterior 'relaxedonehot' / 'relaxedsoftmax')
@@ -1147,6 +1148,14 @@ class VariationalAutoencoder:
         metrics['_grad/' + self.variable_name(k)] = g.clone()
     return out[0], metrics
 
+  def _fit_batch(self, b):
+    """one element of an iterable `train` / `valid` of fit as what optimize takes (MultitaskVAE: also 3-tuples)"""
+    return _as_tensor(b, self.device)
+
+  def _fit_batch_rows(self, xb) -> int:
+    """the batch size of the engine that ran such an element"""
+    return xb.shape[0]
+
   @property
   def nan_flag(self) -> bool:
     """True when a training step met non-finite gradients and skipped its update (host sync)."""
@@ -1227,7 +1236,7 @@ class VariationalAutoencoder:
         ep = 0
         while epochs < 0 or ep < epochs:
           for b in train:
-            yield _as_tensor(b, self.device)
+            yield self._fit_batch(b)
           ep += 1
 
     # ---- validation / logging cadence of Trainer.fit (training/trainer.py:607-700): `valid_interval` > 0 takes
@@ -1249,7 +1258,7 @@ class VariationalAutoencoder:
           yield data[i:i + bs].contiguous()
       else:
         for b in valid:
-          yield _as_tensor(b, self.device)
+          yield self._fit_batch(b)
 
     def run_valid():
       losses, mets = [], {}
@@ -1302,7 +1311,7 @@ class VariationalAutoencoder:
                                     track_gradients=track_gradients,
                                     use_graph=compile_graph and self.device.type == 'cuda')
       it += 1
-      eng = self._engine(xb.shape[0])
+      eng = self._engine(self._fit_batch_rows(xb))
       self.last_train_loss, self.last_train_metrics = loss, metrics
       if on_batch_end is not None:
         on_batch_end()
@@ -2963,11 +2972,296 @@ class TwoStageVAE(BetaVAE):
     net.t = int(self._find_variable(d, 'stage2_optimizer/iter'))
 
 
+# ======================================================================================
+# MultitaskVAE / SkiptaskVAE: semi-supervised label head on the latents (multitask_vae.py)
+# ======================================================================================
+class OneHotCategoricalLabels:
+  """OneHotCategorical(logits) as predict_labels returns it: what callers of the reference read from p(y|z)."""
+
+  def __init__(self, logits: torch.Tensor):
+    self.logits = logits
+    self.event_shape = (int(logits.shape[-1]),)
+    self.batch_shape = tuple(logits.shape[:-1])
+
+  def probs_parameter(self) -> torch.Tensor:
+    return torch.softmax(self.logits, -1)
+
+  def mean(self) -> torch.Tensor:
+    return self.probs_parameter()
+
+  def mode(self) -> torch.Tensor:
+    """one-hot rows at the largest logit (the class index: mode().argmax(-1))"""
+    return torch.nn.functional.one_hot(self.logits.argmax(-1), self.logits.shape[-1]).to(self.logits.dtype)
+
+  def log_prob(self, y) -> torch.Tensor:
+    """sum_k y_k log_softmax(logits)_k (TFP's OneHotCategorical._log_prob: soft labels too)"""
+    y = torch.as_tensor(y, dtype=self.logits.dtype, device=self.logits.device)
+    return (y * torch.log_softmax(self.logits, -1)).sum(-1)
+
+  def sample(self, n=None, seed=None) -> torch.Tensor:
+    g = None if seed is None else torch.Generator(device='cpu').manual_seed(int(seed))   # (None: torch's own stream)
+    pr = self.probs_parameter().reshape(-1, self.logits.shape[-1]).cpu()
+    idx = torch.multinomial(pr, int(n or 1), replacement=True, generator=g).T   # [n, rows]
+    oh = torch.nn.functional.one_hot(idx, self.logits.shape[-1]).to(dtype=self.logits.dtype, device=self.logits.device)
+    oh = oh.reshape((int(n or 1),) + tuple(self.logits.shape))
+    return oh[0] if n is None else oh
+
+
+class MultitaskVAE(AnnealingVAE):
+  """multitask_vae.py:21-207 (Trong et al. 2019): an AnnealingVAE with labels = RVconf(K, 'onehot', projection=True), a
+  Dense(zdim -> K) on a FRESH sample z' of q(z|x) giving the logits of p(y|z').  Inputs are x, (x,) or
+  (x_u, x_s, y_s) with equal halves; a labelled call evaluates
+    loss = -mean_u(llk_u - kl_u) - mean_s(llk_s - kl_s) - alpha * mean_s log p(y_s | z')
+  (the two half-batch means added) as ONE engine step over cat(x_u, x_s).  Built is the form that reads the latents
+  directly (skip_decoder=True, SkiptaskVAE): here the decoder's last layer is the observation's own projection."""
+
+  _tril_refusal = "the label head's fresh sample is written for the 'mvndiag' posterior"
+  _concrete_refusal = _tril_refusal
+  _relaxedbern_refusal = _tril_refusal
+
+  def __init__(self, labels: RVconf = None, encoder_y=None, decoder_y=None, alpha: float = 10., n_semi_iw=(),
+               skip_decoder: bool = False, name: str = 'MultitaskVAE', **kwargs):
+    if labels is None:
+      labels = RVconf(10, 'onehot', projection=True, name='digits')
+    if isinstance(labels, (list, tuple)):
+      raise NotImplementedError('a list of label variables: the label head is ONE OneHotCategorical over the latents')
+    if not isinstance(labels, RVconf):
+      raise ValueError(f'labels must be an RVconf, got {type(labels)}')
+    if str(labels.posterior).lower() not in ('onehot', 'onehotcategorical'):
+      raise NotImplementedError(f"labels posterior {labels.posterior!r}: the label kernel evaluates 'onehot' "
+                                f'(OneHotCategorical) only')
+    if len(tuple(labels.event_shape)) != 1 or not labels.projection:
+      raise NotImplementedError("labels must be RVconf(K, 'onehot', projection=True): one K-way variable behind a Dense "
+                                'projection of the latents')
+    if not skip_decoder:
+      raise NotImplementedError("skip_decoder=False: the decoder's last layer is the observation's projection here, so "
+                                'there is no decoder activation h_d for the labels to read; use SkiptaskVAE')
+    if encoder_y is not None:
+      raise NotImplementedError("encoder_y: a second posterior q(z_y|x) ('tie' / 'copy' / a network) is not built")
+    if decoder_y is not None:
+      raise NotImplementedError('decoder_y: hidden layers between the latents and the labels are not built (MultiheadVAE '
+                                'would add a batch-normalised stack, and the engine has no batch normalisation)')
+    if isinstance(n_semi_iw, (int, np.integer)) and not isinstance(n_semi_iw, bool):
+      raise NotImplementedError(f'n_semi_iw={n_semi_iw}: importance-weighted label samples are not built (n_semi_iw=() '
+                                f'draws the one fresh sample)')
+    if tuple(n_semi_iw) != ():
+      raise NotImplementedError(f'n_semi_iw={n_semi_iw!r}: only () is built')
+    ss = kwargs.get('sample_shape', ())
+    if (ss if isinstance(ss, int) else tuple(ss)) != ():
+      raise NotImplementedError(f'sample_shape={ss!r}: a labelled step lays the batch out as cat(x_u, x_s), the tiled '
+                                f'batch of sample_shape would break the halves apart')
+    self.labels, self.alpha = labels, float(alpha)
+    self.n_semi_iw, self.skip_decoder, self.encoder_y, self.decoder_y = (), True, None, None
+    super().__init__(name=name, **kwargs)
+
+  def _reg_options(self) -> dict:
+    return dict(label_units=int(self.labels.event_size))
+
+  def set_elbo_configs(self, analytic=None, reverse=None, free_bits=None, sample_shape=None):
+    if sample_shape is not None and (sample_shape if isinstance(sample_shape, int) else tuple(sample_shape)) != ():
+      raise NotImplementedError(f'sample_shape={sample_shape!r} is not offered by {type(self).__name__}')
+    return super().set_elbo_configs(analytic=analytic, reverse=reverse, free_bits=free_bits)
+
+  def variable_name(self, key: tuple) -> str:
+    if key[0] == 'lab':
+      return f"{self.labels.name}/{'kernel' if key[-1] == 'w' else 'bias'}"
+    return super().variable_name(key)
+
+  # ---- inputs -----------------------------------------------------------------------------------------------------------
+  def _ssl_inputs(self, inputs):
+    """x | (x,) | (x_u, x_s, y_s) -> (x_u, x_s or None, y_s [B_s, K] float or None)"""
+    if not isinstance(inputs, (tuple, list)):
+      return _as_tensor(inputs, self.device), None, None
+    if len(inputs) == 1:
+      return _as_tensor(inputs[0], self.device), None, None
+    if len(inputs) != 3:
+      raise ValueError(f'inputs must be x, (x,) or (x_u, x_s, y_s): got {len(inputs)} elements')
+    x_u, x_s = _as_tensor(inputs[0], self.device), _as_tensor(inputs[1], self.device)
+    K = int(self.labels.event_size)
+    y = inputs[2]
+    y = y if torch.is_tensor(y) else torch.as_tensor(np.asarray(y))
+    if y.dim() == 1:   # integer classes
+      if y.is_floating_point() and bool((y != y.round()).any()):
+        raise ValueError('labels of one axis must be integer classes')
+      y = y.to(torch.int64)
+      if bool(((y < 0) | (y >= K)).any()):
+        raise ValueError(f'integer labels outside [0, {K})')
+      y = torch.nn.functional.one_hot(y, K)
+    y = y.to(device=self.device, dtype=torch.float32).contiguous()
+    if x_u.shape[0] != x_s.shape[0]:
+      raise ValueError(f'a labelled step needs equal halves: {x_u.shape[0]} unlabelled and {x_s.shape[0]} labelled rows')
+    if tuple(y.shape) != (x_s.shape[0], K):
+      raise ValueError(f'labels: expected [{x_s.shape[0]}, {K}] or [{x_s.shape[0]}], got {tuple(y.shape)}')
+    return x_u, x_s, y
+
+  def _names(self):
+    o, l, y = self.observation.name, self.latents.name, self.labels.name
+    return f'uns/llk_{o}', f'uns/kl_{l}', f'sup/llk_{o}', f'sup/kl_{l}', f'sup/llk_{y}'
+
+  def _fit_batch(self, b):
+    if not isinstance(b, (tuple, list)):
+      return _as_tensor(b, self.device)
+    t = self._ssl_inputs(b)
+    return t[0] if t[1] is None else t
+
+  def _fit_batch_rows(self, xb) -> int:
+    return 2 * xb[0].shape[0] if isinstance(xb, tuple) else xb.shape[0]
+
+  # ---- forward API ------------------------------------------------------------------------------------------------------
+  def encode(self, inputs, training=None, mask=None, only_encoding=False, eps=None, **kwargs):
+    """the labels are never conditioned on: the first (unlabelled) input is encoded (multitask_vae.py:129-142)"""
+    return super().encode(self._ssl_inputs(inputs)[0], training=training, mask=mask, only_encoding=only_encoding,
+                          eps=eps)
+
+  def predict_labels(self, inputs=None, latents=None, training=None, mask=None, n_mcmc=(), mean=False, seed=None,
+                     **kwargs) -> OneHotCategoricalLabels:
+    """multitask_vae.py:95-127 with skip_decoder=True: p(y|z) at the posterior's mean (`mean=True`) or at a fresh sample
+    of it; `latents` may be a posterior or a tensor of codes [n, zdim].  classify: predict_labels(x, mean=True).mode()"""
+    if n_mcmc != ():
+      raise NotImplementedError(f'n_mcmc={n_mcmc!r}: only the single sample () is built')
+    if latents is None:
+      latents = self.encode(inputs, training=training, mask=mask)
+    if isinstance(latents, MVNDiagPosterior):
+      z = latents.mean() if mean else latents.sample(seed=seed)
+    else:
+      z = latents
+    z = _as_tensor(z, self.device).reshape(-1, self.zdim)
+    # (the launch takes any number of rows and needs no per-batch plan: the engine build() made serves)
+    return OneHotCategoricalLabels(self._engine(1).label_logits(z))
+
+  def call(self, inputs, training=None, mask=None, eps=None, **kwargs):
+    """-> ((p(x|z), p(y|z)), q(z|x)) (multitask_vae.py:144-156)"""
+    qz_x = self.encode(inputs, training=training, mask=mask, eps=eps)
+    py_z = self.predict_labels(latents=qz_x, training=training, mask=mask)
+    px_z = self.decode(qz_x, training=training, mask=mask)
+    self._last_outputs = ((px_z, py_z), qz_x)
+    return (px_z, py_z), qz_x
+
+  __call__ = call
+
+  def _labelled_forward(self, x_u, x_s, y, eps, eps_y):
+    x = torch.cat([x_u, x_s]).contiguous()
+    eng = self._engine(x.shape[0])
+    eng.set_labels(y, None if eps_y is None else _as_tensor(eps_y, self.device))
+    eng.set_hyper(beta=self.beta, t=self._step, label_alpha=self.alpha, **self._hyper_extra())
+    eng.forward(x, None if eps is None else _as_tensor(eps, self.device).reshape(x.shape[0], -1))
+    return eng
+
+  def elbo_components(self, inputs, training=None, mask=None, eps=None, eps_y=None, **kwargs):
+    """multitask_vae.py:164-207 + merge_objectives (variational_autoencoder.py:622-632): the unlabelled entries per
+    sample, the labelled ones reduced to scalars; llk['sup/llk_<labels>'] = alpha * mean_s log p(y_s | z')"""
+    x_u, x_s, y = self._ssl_inputs(inputs)
+    n = self._names()
+    if x_s is None:
+      self._engine(x_u.shape[0]).set_labels(None)
+      llk, kl = super().elbo_components(x_u, training=training, mask=mask, eps=eps)
+      return {'uns/' + k: v for k, v in llk.items()}, {'uns/' + k: v for k, v in kl.items()}
+    eng = self._labelled_forward(x_u, x_s, y, eps, eps_y)
+    h = x_u.shape[0]
+    qz_x = MVNDiagPosterior(eng.p[h:].clone(), eng.z[h:].clone(), eng.D)
+    self._last_outputs = ((self._observation_dist(eng.dec.outs[-1][h:].clone()),
+                           OneHotCategoricalLabels(eng.lab_logits.clone())), qz_x)
+    klv = eng.kl.clone() * self.beta
+    llk = {n[0]: eng.llk[:h].clone(), n[2]: eng.llk[h:].mean(), n[4]: -eng.out4[3].clone()}
+    kl = {n[1]: klv[:h].unsqueeze(0) if self.analytic else klv[:h], n[3]: klv[h:].mean()}
+    return llk, kl
+
+  def optimize(self, inputs, training: bool = True, optimizer=None, learning_rate=1e-4,
+               clipnorm=None, clipvalue=None, global_clipnorm=None, skip_update_threshold=None,
+               when_skip_update: int = 0, nan_gradients_policy: str = 'skip',
+               allow_none_gradients=False, aggregate_gradients=False, track_gradients=False,
+               eps=None, use_graph: bool = False, eps_y=None):
+    """Networks.optimize over x, (x,) or (x_u, x_s, y_s).  An unlabelled call is the AnnealingVAE step (the label
+    variables receive a zero gradient); a labelled one runs cat(x_u, x_s) as one engine step whose gradient is the
+    reference's, so every gradient policy acts on it.  `eps` [B_u + B_s, zdim] / `eps_y` [B_s, zdim] fix the noise of z
+    and of the fresh sample z' (tests)."""
+    x_u, x_s, y = self._ssl_inputs(inputs)
+    n = self._names()
+    if x_s is None:
+      assert eps_y is None, 'eps_y belongs to a labelled step'
+      self._engine(x_u.shape[0]).set_labels(None)
+      loss, m = super().optimize(x_u, training=training, learning_rate=learning_rate, clipnorm=clipnorm,
+                                 clipvalue=clipvalue, global_clipnorm=global_clipnorm,
+                                 skip_update_threshold=skip_update_threshold, when_skip_update=when_skip_update,
+                                 nan_gradients_policy=nan_gradients_policy, track_gradients=track_gradients, eps=eps,
+                                 use_graph=use_graph)
+      ren = {f'llk_{self.observation.name}': n[0], f'kl_{self.latents.name}': n[1]}
+      return loss, {ren.get(k, k): v for k, v in m.items()}
+    if nan_gradients_policy not in ('stop', 'skip', 'raise', 'ignore', 'restore'):
+      raise ValueError(f'nan_gradients_policy={nan_gradients_policy!r}')
+    x = torch.cat([x_u, x_s]).contiguous()
+    eng = self._engine(x.shape[0])
+    if eps is not None:
+      eps = _as_tensor(eps, self.device).reshape(x.shape[0], -1)
+    if eps_y is not None:
+      eps_y = _as_tensor(eps_y, self.device).reshape(x_s.shape[0], -1)
+    if training:
+      self._step += 1
+    eng.step_count = self._step - 1 if training else self._step
+    if not training:
+      eng.set_labels(y, eps_y)
+      eng.set_hyper(beta=self.beta, t=self._step, label_alpha=self.alpha, **self._hyper_extra())
+      eng.forward(x, eps)
+    else:
+      eng.train_step(x, eps, lr=self._lr(learning_rate), beta=self.beta, global_clipnorm=global_clipnorm,
+                     use_graph=use_graph, clipnorm=clipnorm, clipvalue=clipvalue,
+                     skip_update_threshold=skip_update_threshold, when_skip_update=when_skip_update,
+                     check_nan=nan_gradients_policy != 'ignore', labels=y, eps_y=eps_y, label_alpha=self.alpha,
+                     **self._hyper_extra())
+      self._step = eng.step_count
+    o = eng.label_step_outputs(self.beta)
+    metrics = {n[0]: o['uns/llk'], n[1]: o['uns/kl'], n[2]: o['sup/llk'], n[3]: o['sup/kl'], n[4]: o['sup/llk_y']}
+    if training and track_gradients:
+      for k, g in eng.grad_views().items():
+        metrics['_grad/' + self.variable_name(k)] = g.clone()
+    return o['loss'], metrics
+
+  # ---- checkpoints: the label variables travel with every other parameter; their Adam slots beside them -------------------
+  def _label_slots(self):
+    eng = self._engine(1)
+    for key, shp, off in eng.layout.entries:
+      if key[0] == 'lab':
+        n = int(np.prod(shp))
+        yield f'optimizer/{self.variable_name(key)}', eng.m[off:off + n].view(shp), eng.v[off:off + n].view(shp)
+
+  def _extra_checkpoint_variables(self) -> Dict[str, np.ndarray]:
+    W = {}
+    for name, m, v in self._label_slots():
+      W[f'{name}/m'] = m.detach().cpu().numpy()
+      W[f'{name}/v'] = v.detach().cpu().numpy()
+    return W
+
+  def _load_extra_checkpoint_variables(self, d: Dict[str, np.ndarray]):
+    for name, m, v in self._label_slots():
+      for slot, dst in (('m', m), ('v', v)):
+        nm = f'{name}/{slot}'
+        if nm in d or any(k.endswith('/' + nm) for k in d):   # (a checkpoint without the slots: they stay as they are)
+          dst.copy_(torch.as_tensor(np.asarray(self._find_variable(d, nm)), dtype=torch.float32, device=self.device))
+
+
+class SkiptaskVAE(MultitaskVAE):
+  """multitask_vae.py:226-240: the labels read the latents directly (skip_decoder=True, no decoder_y)"""
+
+  def __init__(self, encoder_y=None, name: str = 'SkiptaskVAE', **kwargs):
+    kwargs.pop('skip_decoder', None)
+    kwargs.pop('decoder_y', None)
+    super().__init__(encoder_y=encoder_y, decoder_y=None, skip_decoder=True, name=name, **kwargs)
+
+
+class MultiheadVAE(MultitaskVAE):
+  """multitask_vae.py:243-264: refused -- its decoder_y is a batch-normalised Dense stack, and the engine has no batch
+  normalisation"""
+
+  def __init__(self, decoder_y=None, name: str = 'MultiheadVAE', **kwargs):
+    raise NotImplementedError('MultiheadVAE: its decoder_y is a batch-normalised Dense stack (NetConf((512, 512), '
+                              'batchnorm=True)); the engine has no batch normalisation -- use SkiptaskVAE')
+
+
 def get_vae(name: str):
   """odin/bay/vi/autoencoder/__init__.py:28"""
   table = {c.__name__.lower(): c for c in (VariationalAutoencoder, BetaVAE, AnnealingVAE,
                                            BetaTCVAE, FactorVAE, BetaCapacityVAE, InfoVAE, DIPVAE,
-                                           VampriorVAE, VQVAE, TwoStageVAE)}
+                                           VampriorVAE, VQVAE, TwoStageVAE, MultitaskVAE, SkiptaskVAE)}
   table['vae'] = VariationalAutoencoder
   key = str(name).lower().replace('_', '')
   if key not in table:
