@@ -440,6 +440,27 @@ int odin_wgrad_pair_end(void);
 int odin_neck_rows(int B, int P, int D, int C0);
 int odin_neck_fwd(const odin_neck_args* a, void* stream);
 int odin_neck_bwd(const odin_neck_args* a, void* stream);
+/* odin_neck_bwd whose launch also executes a part of the step's slab reduction, on the CUs the neck's workgroups (one
+ * per CU on half of the chip, latency bound) leave idle.  jobs / n_jobs / g / g_n / part: the WHOLE job list of the step,
+ * as the step's odin_slab_reduce_sumsq would be given it (at most 64 jobs); early_mask (bit j = job j): the jobs whose
+ * slabs are complete before this launch.  ONE plan is made over all jobs, exactly odin_slab_reduce_sumsq's (grid width,
+ * every job's slice of the norm partials); n_reducers extra workgroups (< 0:
+ * odin_neck_reduce_workgroups' count) execute the early jobs of it -- same code, same rows, same order, partials at the same
+ * indices -- and odin_slab_reduce_sumsq_masked(jobs, n_jobs, early_mask, ...) executes the others and stages the hyper
+ * row.  Together bit-identical to odin_neck_bwd + odin_slab_reduce_sumsq.  Of a job outside early_mask only dst, n,
+ * stride and the alignment of src are read here.  No workgroup waits for another; a reducing workgroup touches none of
+ * the neck's tensors.  part == NULL: dry run, nothing is launched (the count: odin_slab_reduce_sumsq_masked's dry run).
+ * early_mask == 0: odin_neck_bwd's launch.  -2, nothing launched: more than 64 jobs, a mask beyond the list, an early
+ * job whose dst lies outside [g, g + g_n) -- the range-word reset among them --, n_reducers < 0 where
+ * odin_neck_reduce_workgroups gives 0.
+ * odin_neck_reduce_workgroups: the reducers the launch takes by itself -- one per four virtual blocks of the early jobs,
+ * so that each walks one step (the measured regime) -- if the neck's own workgroups (one per CU) leave that many CUs
+ * free; else 0, as for arguments the launch rejects: the caller keeps odin_neck_bwd and the plain reduction (on 256 CUs
+ * with the dSprites decoder: from B = 286 on). */
+int odin_neck_reduce_workgroups(const odin_neck_args* a, const odin_reduce_job* jobs, int n_jobs, uint64_t early_mask,
+                                const float* g, size_t g_n);
+int odin_neck_bwd_reduce(const odin_neck_args* a, const odin_reduce_job* jobs, int n_jobs, uint64_t early_mask,
+                         const float* g, size_t g_n, float* part, int n_reducers, void* stream);
 
 /* ---- the discriminator's head with its loss in ONE launch (round 6; thin_dense.hip): Dense(K -> 1) on h [B, K]
  * (factor_discriminator.py:60-95: the last layer of FactorDiscriminator), the mean it feeds, and the layer's backward:
@@ -798,6 +819,13 @@ int odin_sumsq_adam_ring(float* theta, const float* g, float* m, float* v, size_
  * odin_slab_reduce + odin_sumsq_adam_ring (three launches -> two; base_networks.py:584-596). */
 int odin_slab_reduce_sumsq(const odin_reduce_job* jobs, int n_jobs, const float* g, size_t g_n, float* part,
                            int* n_parts_out, const float* stage_src, float* stage_dst, int stage_n, void* stream);
+/* The same launch without the jobs in skip_mask (bit j = job j; executed by odin_neck_bwd_reduce): same grid width, the
+ * other jobs' partials at the indices the whole plan gives them, the skipped jobs' slices of `part` and their
+ * destinations untouched, *n_parts_out = the count of the WHOLE list (the same with and without the mask).  At most 64
+ * jobs; a skipped job's dst must lie inside [g, g + g_n): -2 otherwise, nothing launched. */
+int odin_slab_reduce_sumsq_masked(const odin_reduce_job* jobs, int n_jobs, uint64_t skip_mask, const float* g, size_t g_n,
+                                  float* part, int* n_parts_out, const float* stage_src, float* stage_dst, int stage_n,
+                                  void* stream);
 int odin_adam_ring_parts(float* theta, const float* g, float* m, float* v, size_t n, const float* staged,
                          int alpha_off, int elbo_off, const float* parts, int n_parts, float* gnorm2_out, float clip,
                          int32_t* flag, const float* llk_part, int n_part, const float* kl, const float* tc, float* llk,

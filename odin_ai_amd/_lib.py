@@ -118,6 +118,8 @@ SIGNATURES = {
     'odin_neck_rows': [I, I, I, I],
     'odin_neck_fwd': [C.POINTER(NeckArgs), P],
     'odin_neck_bwd': [C.POINTER(NeckArgs), P],
+    'odin_neck_reduce_workgroups': [C.POINTER(NeckArgs), C.POINTER(ReduceJob), I, C.c_uint64, P, C.c_size_t],
+    'odin_neck_bwd_reduce': [C.POINTER(NeckArgs), C.POINTER(ReduceJob), I, C.c_uint64, P, C.c_size_t, P, I, P],
     'odin_elbo_bernoulli_fwd_bwd': [P, P, P, P, P, I, I, IP, P],
     'odin_elbo_bernoulli_fwd_bwd_ranged': [P, P, P, P, P, I, I, IP, P, P],
     'odin_elbo_cbernoulli_fwd_bwd': [P, P, P, P, P, I, I, IP, P, P],
@@ -179,6 +181,7 @@ SIGNATURES = {
     'odin_sumsq_adam_finalize_flat': [P, P, P, P, C.c_size_t, P, P, P, F, P, P, I, P, P, P, P, P, I, P],
     'odin_sumsq_adam_ring': [P, P, P, P, C.c_size_t, P, P, P, F, P, P, I, P, P, P, P, P, I, P, P, P, I, I, I, P],
     'odin_slab_reduce_sumsq': [P, I, P, C.c_size_t, P, IP, P, P, I, P],
+    'odin_slab_reduce_sumsq_masked': [P, I, C.c_uint64, P, C.c_size_t, P, IP, P, P, I, P],
     'odin_adam_ring_parts': [P, P, P, P, C.c_size_t, P, I, I, P, I, P, F, P, P, I, P, P, P, P, I, P, P, I, I, I, P],
     'odin_rng_normal': [P, C.c_size_t, C.c_uint64, P, P],
     'odin_gather_normalize_u8': [P, P, P, I, I, F, I, P],
@@ -202,7 +205,7 @@ SIGNATURES = {
 VALUE_RETURNING = ('odin_version', 'odin_comm_library', 'odin_conv2d_dgrad_keeps_range',
                    'odin_deconv2d_dgrad_keeps_range', 'odin_bernoulli_tail_keeps_range', 'odin_dense_dgrad_keeps_range', 'odin_conv2d_reads_x_range',
                    'odin_deconv2d_reads_x_range', 'odin_dense_reads_x_range', 'odin_max_slab_rows', 'odin_debug_absmax_fallbacks', 'odin_crc32c', 'odin_debug_last_path',
-                   'odin_latent_block_rows', 'odin_neck_rows', 'odin_debug_igemm_h_ldsw_steps', 'odin_total_correlation_workspace', 'odin_mmd_workspace', 'odin_dip_workspace', 'odin_vamprior_workspace', 'odin_vq_workspace', 'odin_debug_igemm_h_min_flop', 'odin_debug_blk_min_flop',
+                   'odin_latent_block_rows', 'odin_neck_rows', 'odin_neck_reduce_workgroups', 'odin_debug_igemm_h_ldsw_steps', 'odin_total_correlation_workspace', 'odin_mmd_workspace', 'odin_dip_workspace', 'odin_vamprior_workspace', 'odin_vq_workspace', 'odin_debug_igemm_h_min_flop', 'odin_debug_blk_min_flop',
                    'odin_debug_blk_planes', 'odin_debug_blk_first', 'odin_debug_dense_hw_min_tiles', 'odin_gaussian_tail_applicable', 'odin_disc_head_rows', 'odin_debug_mel_r16', 'odin_debug_smallc_planes')
 # entry points declared `void` in include/odin_hip.h
 VOID_RETURNING = ('odin_wgrad_planes_defer_begin', 'odin_wgrad_pair_begin')

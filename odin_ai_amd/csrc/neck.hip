@@ -30,6 +30,7 @@
 #include "odin_device.h"
 #include "odin_internal.h"
 #include "odin_latent_math.h"
+#include "slab_reduce.h"
 #include <cstdint>
 #include <cstdlib>
 #include <utility>
@@ -509,9 +510,53 @@ struct NKBwdLds {
   }
 };
 
+// The REDUCING role of the backward launch (odin_neck_bwd_reduce): workgroups blockIdx.x >= rows execute a part of the
+// step's slab-reduction plan -- the jobs whose slabs were complete before this launch -- while the neck's own workgroups,
+// one per CU on half of the CUs and bound by one CU's L2 stream, leave the other CUs and the HBM idle.  `jobs` holds those
+// jobs with their slices of the norm partials exactly as the step's reduction launch would see them (slab_reduce.h:
+// odin_slab_reduce_plan), `vgx` is that launch's grid width, vb0[j] .. vb0[j + 1] the virtual blocks of job j (its ACTIVE
+// workgroups there: the others write nothing).  A reducer workgroup is four 256-thread virtual blocks and walks the
+// virtual blocks in a fixed stride; nothing here reads or writes what a neck workgroup touches, and no workgroup waits
+// for another.
+struct NeckReduce {
+  ReduceJobs jobs;
+  int vb0[MAX_JOBS + 1];
+  int nj, nvb, vgx, trips;   // trips: column steps of the longest virtual block (1 unless a job is wider than the grid)
+  int rows;                  // the neck's own workgroups: blockIdx.x < rows
+};
+constexpr int NK_RED_LDS = 4096 + 16;   // per virtual block: one 256 x float4 buffer for the path taken, the partial's four floats
+
+__device__ __forceinline__ void neck_reduce_role(const NeckReduce& r, char* sm) {
+  const unsigned tid = threadIdx.x & 255u;
+#ifdef ODIN_SIM
+  const int sub = threadIdx.x >> 8;
+#else
+  const int sub = __builtin_amdgcn_readfirstlane(threadIdx.x >> 8);
+#endif
+  char* base = sm + sub * NK_RED_LDS;
+  const SlabLds L{reinterpret_cast<float4*>(base), reinterpret_cast<float4*>(base), reinterpret_cast<float*>(base),
+                  reinterpret_cast<float*>(base + 4096)};
+  const int nred = (int)gridDim.x - r.rows, w = (int)blockIdx.x - r.rows;
+  // (workgroup-uniform trip count: the body's barriers are the whole workgroup's)
+  for (int v0 = 4 * w; v0 < r.nvb; v0 += 4 * nred) {
+    const int v = v0 + sub;
+    const bool live = v < r.nvb;
+    int j = 0;
+    if (live)
+      while (j + 1 < r.nj && v >= r.vb0[j + 1]) ++j;
+    unsigned t = tid;
+#ifndef ODIN_SIM
+    // (the lane id is opaque per step: hoisted out of this loop, the three paths' per-lane row offsets are all live at
+    // once and spill -- this kernel has 128 registers per lane)
+    asm volatile("" : "+v"(t));
+#endif
+    slab_reduce_body<true>(r.jobs, (unsigned)j, (unsigned)(live ? v - r.vb0[j] : 0), (unsigned)r.vgx, t, r.trips, live, L);
+  }
+}
+
+// the backward pass of one neck workgroup (the two kernels below)
 template <int C0, int NQ>   // NQ = P / 32: float4 columns of a W4 row per lane of its 8-lane group (4: P = 128, 8: P = 256)
-__global__ __launch_bounds__(NK_NT) void neck_bwd_kernel(NeckFwd q) {
-  ODIN_DYN_SMEM(char, sm);
+__device__ __forceinline__ void neck_bwd_body(const NeckFwd& q, char* sm) {
   const odin_neck_args& a = q.a;
   const int P = a.P, D = a.D, J = 2 * a.D, N0 = NK_OP * C0;
   const NKBwdLds L(P, D, C0);
@@ -984,6 +1029,25 @@ __global__ __launch_bounds__(NK_NT) void neck_bwd_kernel(NeckFwd q) {
   NK_STAMP(17);
 }
 
+// odin_neck_bwd's launch: the instances every engine without reducers runs (Shapes3D, FactorVAE, CelebA; argument block
+// and code as before the reducing role existed)
+template <int C0, int NQ>
+__global__ __launch_bounds__(NK_NT) void neck_bwd_kernel(NeckFwd q) {
+  ODIN_DYN_SMEM(char, sm);
+  neck_bwd_body<C0, NQ>(q, sm);
+}
+
+// odin_neck_bwd_reduce's launch: workgroups blockIdx.x < r.rows are the neck's, the others reduce
+template <int C0, int NQ>
+__global__ __launch_bounds__(NK_NT) void neck_bwd_reduce_kernel(NeckFwd q, NeckReduce r) {
+  ODIN_DYN_SMEM(char, sm);
+  if ((int)blockIdx.x >= r.rows) {
+    neck_reduce_role(r, sm);
+    return;
+  }
+  neck_bwd_body<C0, NQ>(q, sm);
+}
+
 template <typename K>
 int nk_set_lds(K kern, size_t bytes) {
 #ifndef ODIN_SIM
@@ -1018,7 +1082,8 @@ extern "C" int odin_debug_set_neck_stamps(void* buf) {
   return 0;
 }
 
-extern "C" int odin_neck_bwd(const odin_neck_args* args, void* stream) {
+// rd == nullptr: the launch of rows workgroups; else n_red more that execute rd's jobs (neck_reduce_role)
+static int neck_bwd_launch(const odin_neck_args* args, NeckReduce* rd, int n_red, const char* what, void* stream) {
   const odin_neck_args& a = *args;
   const int rows = odin_neck_rows(a.B, a.P, a.D, a.C0);
   if (rows == 0) return odin_fail(-2, "neck_bwd: shapes outside the fused regime");
@@ -1031,18 +1096,100 @@ extern "C" int odin_neck_bwd(const odin_neck_args* args, void* stream) {
   q.w1_al = (((size_t)a.w1) & 15) == 0;
   q.stamps = g_nk_stamps;
   const NKBwdLds L(a.P, a.D, a.C0);
-  const size_t lds = (size_t)L.end;
-#define NK_BWD(C0_, NQ_)                                                                  \
-  do {                                                                                    \
-    if (int rc = nk_set_lds(&neck_bwd_kernel<C0_, NQ_>, lds)) return rc;                  \
-    ODIN_LAUNCH((neck_bwd_kernel<C0_, NQ_>), dim3(rows), dim3(NK_NT), lds, stream, q);    \
+  const size_t lds = (size_t)L.end;   // (>= 100 KB: the reducing role's 4 x NK_RED_LDS bytes fit in any instance)
+#define NK_BWD(C0_, NQ_)                                                                                     \
+  do {                                                                                                       \
+    if (rd == nullptr) {                                                                                     \
+      if (int rc = nk_set_lds(&neck_bwd_kernel<C0_, NQ_>, lds)) return rc;                                   \
+      ODIN_LAUNCH((neck_bwd_kernel<C0_, NQ_>), dim3(rows), dim3(NK_NT), lds, stream, q);                     \
+    } else {                                                                                                 \
+      rd->rows = rows;                                                                                       \
+      const NeckReduce& r = *rd;                                                                             \
+      if (int rc = nk_set_lds(&neck_bwd_reduce_kernel<C0_, NQ_>, lds)) return rc;                            \
+      ODIN_LAUNCH((neck_bwd_reduce_kernel<C0_, NQ_>), dim3(rows + n_red), dim3(NK_NT), lds, stream, q, r);   \
+    }                                                                                                        \
   } while (0)
   if (a.C0 == 8 && a.P == 128) NK_BWD(8, 4);
   else if (a.C0 == 8) NK_BWD(8, 8);
   else if (a.P == 128) NK_BWD(16, 4);
   else NK_BWD(16, 8);
 #undef NK_BWD
-  return odin_check_launch("neck_bwd");
+  return odin_check_launch(what);
+}
+
+extern "C" int odin_neck_bwd(const odin_neck_args* args, void* stream) {
+  return neck_bwd_launch(args, nullptr, 0, "neck_bwd", stream);
+}
+
+// the checks of odin_neck_bwd_reduce and the plan over ALL jobs, of which the launch keeps the early ones (= skips the
+// others); *rows_out: the neck's workgroups
+static int neck_reduce_plan(const odin_neck_args* args, const odin_reduce_job* jobs, int n_jobs, uint64_t early_mask,
+                            const float* g, size_t g_n, float* part, NeckReduce* r, int* rows_out) {
+  if (g == nullptr) return odin_fail(-2, "neck_bwd_reduce: no gradient buffer");
+  if (n_jobs < 0 || n_jobs > MAX_JOBS) return odin_fail(-2, "neck_bwd_reduce: more than 64 jobs");
+  if (n_jobs < 64 && (early_mask >> n_jobs) != 0) return odin_fail(-2, "neck_bwd_reduce: mask beyond the jobs");
+  for (int j = 0; j < n_jobs; ++j)
+    if (((early_mask >> j) & 1) && !(jobs[j].dst >= g && jobs[j].dst + jobs[j].n <= g + g_n))
+      return odin_fail(-2, "neck_bwd_reduce: an early job writes outside the gradient buffer");
+  *rows_out = odin_neck_rows(args->B, args->P, args->D, args->C0);
+  if (*rows_out == 0) return odin_fail(-2, "neck_bwd: shapes outside the fused regime");
+  memset(r, 0, sizeof(*r));
+  r->trips = 1;
+  if (early_mask == 0) return 0;
+  int gx = 1;
+  const uint64_t all = n_jobs == 64 ? ~0ull : ((1ull << n_jobs) - 1);
+  if (int rc = odin_slab_reduce_plan(jobs, n_jobs, all & ~early_mask, g, g_n, part, &r->jobs, &r->nj, &gx, nullptr)) return rc;
+  r->vgx = gx;
+  for (int j = 0; j < r->nj; ++j) {
+    int t = 1;
+    r->vb0[j + 1] = r->vb0[j] + odin_reduce_active_blocks(r->jobs.j[j], gx, &t);   // (== pcnt[j]: early jobs lie inside g)
+    if (t > r->trips) r->trips = t;
+  }
+  r->nvb = r->vb0[r->nj];
+  return 0;
+}
+
+// The reducer workgroups odin_neck_bwd_reduce takes by itself (n_reducers < 0) for these arguments: one per four virtual
+// blocks, so that a reducer walks ONE step -- the only regime that was measured (dSprites, B = 256: 114 reducers beside
+// 128 neck workgroups) -- provided the neck's own workgroups leave that many CUs; 0 otherwise (and for arguments the
+// entry rejects): with fewer reducers a few workgroups, at one CU's bandwidth each and queued behind the neck's for
+// the LDS, would walk all of the slabs -- from B = 2 (CUs - reducers) on the caller keeps the two plain launches.
+extern "C" int odin_neck_reduce_workgroups(const odin_neck_args* args, const odin_reduce_job* jobs, int n_jobs,
+                                           uint64_t early_mask, const float* g, size_t g_n) {
+  NeckReduce r;
+  int rows = 0;
+  if (neck_reduce_plan(args, jobs, n_jobs, early_mask, g, g_n, nullptr, &r, &rows) != 0) return 0;
+  const int need = (r.nvb + 3) / 4;
+  return need <= odin_num_cus() - rows ? need : 0;
+}
+
+// odin_neck_bwd whose launch also executes a part of the step's slab reduction: `jobs` is the WHOLE job list of the step
+// as odin_slab_reduce_sumsq(jobs, n_jobs, g, g_n, part, ...) will be given it (at most 64 jobs; of the jobs outside
+// early_mask only dst, n, stride and the alignment of src are read: they decide the plan), early_mask (bit j = job j) the
+// jobs whose slabs are complete before this launch.  Those are reduced here, by n_reducers extra workgroups (< 0:
+// odin_neck_reduce_workgroups' count), with their norm partials in the slices of `part` the whole plan gives them;
+// odin_slab_reduce_sumsq_masked with the same arguments does the rest.  Bit-identical to odin_neck_bwd followed by
+// odin_slab_reduce_sumsq.  part == NULL: dry run, nothing is launched.  early_mask == 0: odin_neck_bwd's launch.
+// -2 (nothing launched): more than 64 jobs, an early job whose dst lies outside [g, g + g_n) (the range-word reset among
+// them), a mask beyond the list, n_reducers < 0 where odin_neck_reduce_workgroups gives 0.
+extern "C" int odin_neck_bwd_reduce(const odin_neck_args* args, const odin_reduce_job* jobs, int n_jobs,
+                                    uint64_t early_mask, const float* g, size_t g_n, float* part, int n_reducers,
+                                    void* stream) {
+  NeckReduce r;
+  int rows = 0;
+  if (int rc = neck_reduce_plan(args, jobs, n_jobs, early_mask, g, g_n, part, &r, &rows)) return rc;
+  int n_red = n_reducers;
+  if (n_red < 0 && r.nvb > 0) {
+    n_red = (r.nvb + 3) / 4;
+    if (n_red > odin_num_cus() - rows)
+      return odin_fail(-2, "neck_bwd_reduce: the neck's workgroups leave too few CUs for one reducer per four virtual blocks");
+  }
+  if (part == nullptr) return 0;
+  if (early_mask == 0 || r.nvb == 0) return neck_bwd_launch(args, nullptr, 0, "neck_bwd", stream);   // (or early jobs of no elements)
+  if (int rc = odin_wgrad_planes_flush(stream)) return rc;  // (deferred weight gradients write the slabs read here)
+  if (n_red < 1) n_red = 1;   // (the early jobs are this launch's to execute)
+  if (n_red > 4096) n_red = 4096;
+  return neck_bwd_launch(args, &r, n_red, "neck_bwd_reduce", stream);
 }
 
 extern "C" int odin_neck_fwd(const odin_neck_args* args, void* stream) {

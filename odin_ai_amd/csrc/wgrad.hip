@@ -20,6 +20,7 @@
 // order (bit-reproducible, no float atomics).
 #include "odin_device.h"
 #include "odin_internal.h"
+#include "slab_reduce.h"
 #include <cstdlib>
 
 // 16 KB of zeros in HBM: the DMA source for SAME-padding rows
@@ -1092,181 +1093,16 @@ int launch_wgrad(WParams& p, int* rows_out, void* stream) {
   return launch_winst<NACC, 9, 2, 8>(p, grid, lds, stream);
 }
 
-constexpr int MAX_JOBS = 64;
-struct ReduceJobs {
-  odin_reduce_job j[MAX_JOBS];
-  // odin_slab_reduce_sumsq: the squared norm of what the launch writes, as one partial per ACTIVE workgroup --
-  // part[poff[j] + blockIdx.x] for blockIdx.x < pcnt[j]; poff[j] < 0: job j's result is not part of the gradient
-  // (the range-word reset).  stage_src / stage_dst: `stage_n` floats copied by workgroup (0, 0) (the step's
-  // hyper-parameter row, read by the Adam launch after `hyper` itself was advanced).
-  float* part;
-  int poff[MAX_JOBS];
-  int pcnt[MAX_JOBS];
-  const float* stage_src;
-  float* stage_dst;
-  int stage_n;
-};
-
-// Vector jobs (n, stride multiples of 4, 16-byte aligned): a block owns 64 consecutive floats of
-// the result; thread (tx = tid & 15, ty = tid >> 4) sums rows ty, ty + 16, ... of float4 column tx
-// with four independent partial sums, the 16 row phases are combined through LDS in a fixed
-// order.  Parallelism is rows x n, not n: a 16 K-float gradient over 256 slab rows is 256 blocks
-// of 16-byte loads instead of 64 blocks of serial 4-byte loads.  Other jobs (bias rows, the
-// tail's 65-float row): one thread per result element.
+// (the job table and the workgroup body: slab_reduce.h -- the neck's backward launch runs the same body for the jobs it
+// reduces early)
 __global__ __launch_bounds__(256) void slab_reduce_kernel(ReduceJobs jobs) {
-  const odin_reduce_job jb = jobs.j[blockIdx.y];
-  const size_t st = jb.stride > 0 ? (size_t)jb.stride : (size_t)jb.n;
+  __shared__ float4 partw[256];
+  __shared__ float4 part[256];
+  __shared__ float parts[256];
+  __shared__ float ssw[4];
   if (jobs.stage_dst != nullptr && blockIdx.x == 0 && blockIdx.y == 0 && (int)threadIdx.x < jobs.stage_n)
     jobs.stage_dst[threadIdx.x] = jobs.stage_src[threadIdx.x];
-  float ss = 0.f;   // squares of what this thread writes (odin_slab_reduce_sumsq)
-  const bool vec = ((jb.n & 3) == 0) && ((st & 3) == 0) &&
-                   ((((size_t)jb.src | (size_t)jb.dst) & 15) == 0);
-  if (vec && (jb.n >> 2) >= 1024) {
-    // wide jobs (weight tensors): a block owns 256 consecutive floats; every wave-instruction
-    // reads one full KB of a slab row, 8 rows in flight per lane, the 4 waves split the rows
-    __shared__ float4 partw[256];
-    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-    const int n4 = jb.n >> 2;
-    const size_t st4 = st >> 2;
-    for (int c0 = blockIdx.x * 64; c0 < n4; c0 += gridDim.x * 64) {  // block-uniform
-      const int c = c0 + tx;
-      float4 a[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) a[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (c < n4) {
-        const float4* s = reinterpret_cast<const float4*>(jb.src) + c;
-        int g = ty;
-        for (; g + 28 < jb.rows; g += 32) {
-          float4 v[8];
-#pragma unroll
-          for (int u = 0; u < 8; ++u) v[u] = s[(size_t)(g + 4 * u) * st4];
-#pragma unroll
-          for (int u = 0; u < 8; ++u) {
-            a[u].x += v[u].x; a[u].y += v[u].y; a[u].z += v[u].z; a[u].w += v[u].w;
-          }
-        }
-        for (; g < jb.rows; g += 4) {
-          const float4 v0 = s[(size_t)g * st4];
-          a[0].x += v0.x; a[0].y += v0.y; a[0].z += v0.z; a[0].w += v0.w;
-        }
-      }
-      float4 t;
-      t.x = ((a[0].x + a[1].x) + (a[2].x + a[3].x)) + ((a[4].x + a[5].x) + (a[6].x + a[7].x));
-      t.y = ((a[0].y + a[1].y) + (a[2].y + a[3].y)) + ((a[4].y + a[5].y) + (a[6].y + a[7].y));
-      t.z = ((a[0].z + a[1].z) + (a[2].z + a[3].z)) + ((a[4].z + a[5].z) + (a[6].z + a[7].z));
-      t.w = ((a[0].w + a[1].w) + (a[2].w + a[3].w)) + ((a[4].w + a[5].w) + (a[6].w + a[7].w));
-      partw[threadIdx.x] = t;
-      __syncthreads();
-      if (ty == 0 && c < n4) {
-        const float4 q1 = partw[64 + tx], q2 = partw[128 + tx], q3 = partw[192 + tx];
-        t.x = (t.x + q1.x) + (q2.x + q3.x);
-        t.y = (t.y + q1.y) + (q2.y + q3.y);
-        t.z = (t.z + q1.z) + (q2.z + q3.z);
-        t.w = (t.w + q1.w) + (q2.w + q3.w);
-        reinterpret_cast<float4*>(jb.dst)[c] = t;
-        ss += (t.x * t.x + t.y * t.y) + (t.z * t.z + t.w * t.w);
-      }
-      __syncthreads();
-    }
-  } else if (vec) {
-    __shared__ float4 part[256];
-    const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
-    const int n4 = jb.n >> 2;
-    for (int c0 = blockIdx.x * 16; c0 < n4; c0 += gridDim.x * 16) {  // block-uniform
-      const int c = c0 + tx;
-      float4 a0 = make_float4(0.f, 0.f, 0.f, 0.f), a1 = a0, a2 = a0, a3 = a0;
-      if (c < n4) {
-        const float4* s = reinterpret_cast<const float4*>(jb.src) + c;
-        const size_t st4 = st >> 2;
-        int g = ty;
-        for (; g + 112 < jb.rows; g += 128) {  // 8 rows in flight
-          const float4 v0 = s[(size_t)g * st4], v1 = s[(size_t)(g + 16) * st4];
-          const float4 v2 = s[(size_t)(g + 32) * st4], v3 = s[(size_t)(g + 48) * st4];
-          const float4 v4 = s[(size_t)(g + 64) * st4], v5 = s[(size_t)(g + 80) * st4];
-          const float4 v6 = s[(size_t)(g + 96) * st4], v7 = s[(size_t)(g + 112) * st4];
-          a0.x += v0.x; a0.y += v0.y; a0.z += v0.z; a0.w += v0.w;
-          a1.x += v1.x; a1.y += v1.y; a1.z += v1.z; a1.w += v1.w;
-          a2.x += v2.x; a2.y += v2.y; a2.z += v2.z; a2.w += v2.w;
-          a3.x += v3.x; a3.y += v3.y; a3.z += v3.z; a3.w += v3.w;
-          a0.x += v4.x; a0.y += v4.y; a0.z += v4.z; a0.w += v4.w;
-          a1.x += v5.x; a1.y += v5.y; a1.z += v5.z; a1.w += v5.w;
-          a2.x += v6.x; a2.y += v6.y; a2.z += v6.z; a2.w += v6.w;
-          a3.x += v7.x; a3.y += v7.y; a3.z += v7.z; a3.w += v7.w;
-        }
-        for (; g + 48 < jb.rows; g += 64) {
-          const float4 v0 = s[(size_t)g * st4], v1 = s[(size_t)(g + 16) * st4];
-          const float4 v2 = s[(size_t)(g + 32) * st4], v3 = s[(size_t)(g + 48) * st4];
-          a0.x += v0.x; a0.y += v0.y; a0.z += v0.z; a0.w += v0.w;
-          a1.x += v1.x; a1.y += v1.y; a1.z += v1.z; a1.w += v1.w;
-          a2.x += v2.x; a2.y += v2.y; a2.z += v2.z; a2.w += v2.w;
-          a3.x += v3.x; a3.y += v3.y; a3.z += v3.z; a3.w += v3.w;
-        }
-        for (; g < jb.rows; g += 16) {
-          const float4 v0 = s[(size_t)g * st4];
-          a0.x += v0.x; a0.y += v0.y; a0.z += v0.z; a0.w += v0.w;
-        }
-      }
-      part[threadIdx.x] = make_float4((a0.x + a1.x) + (a2.x + a3.x), (a0.y + a1.y) + (a2.y + a3.y),
-                                      (a0.z + a1.z) + (a2.z + a3.z), (a0.w + a1.w) + (a2.w + a3.w));
-      __syncthreads();
-      if (ty == 0 && c < n4) {
-        float4 t = part[tx];
-#pragma unroll
-        for (int u = 1; u < 16; ++u) {
-          const float4 q = part[u * 16 + tx];
-          t.x += q.x; t.y += q.y; t.z += q.z; t.w += q.w;
-        }
-        reinterpret_cast<float4*>(jb.dst)[c] = t;
-        ss += (t.x * t.x + t.y * t.y) + (t.z * t.z + t.w * t.w);
-      }
-      __syncthreads();
-    }
-  } else
-  // odd-sized jobs (the fused tail's 65-float rows, 33-float heads): 32 result elements per block,
-  // 8 row phases per element, 8 loads in flight per thread -- a one-thread-per-element loop walks
-  // 256+ rows serially (dozens of dependent L2 round trips: it set the duration of the whole launch)
-  {
-    __shared__ float parts[256];
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-    for (int i0 = blockIdx.x * 32; i0 < jb.n; i0 += gridDim.x * 32) {  // block-uniform
-      const int i = i0 + tx;
-      float a[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) a[u] = 0.f;
-      if (i < jb.n) {
-        const float* s = jb.src + i;
-        int g = ty;
-        for (; g + 56 < jb.rows; g += 64) {
-          float v[8];
-#pragma unroll
-          for (int u = 0; u < 8; ++u) v[u] = s[(size_t)(g + 8 * u) * st];
-#pragma unroll
-          for (int u = 0; u < 8; ++u) a[u] += v[u];
-        }
-        for (; g < jb.rows; g += 8) a[0] += s[(size_t)g * st];
-      }
-      parts[threadIdx.x] = ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7]));
-      __syncthreads();
-      if (ty == 0 && i < jb.n) {
-        float t = parts[tx];
-#pragma unroll
-        for (int u = 1; u < 8; ++u) t += parts[u * 32 + tx];
-        jb.dst[i] = t;
-        ss += t * t;
-      }
-      __syncthreads();
-    }
-  }
-  if (jobs.part != nullptr && jobs.poff[blockIdx.y] >= 0 && (int)blockIdx.x < jobs.pcnt[blockIdx.y]) {
-    // one partial per active workgroup, fixed order inside the workgroup: wave sums by shuffles, then the four waves
-    __shared__ float ssw[4];
-    float v = ss;
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-    if ((threadIdx.x & 63) == 0) ssw[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) jobs.part[jobs.poff[blockIdx.y] + blockIdx.x] = (ssw[0] + ssw[1]) + (ssw[2] + ssw[3]);
-  }
+  slab_reduce_body<false>(jobs, blockIdx.y, blockIdx.x, gridDim.x, threadIdx.x, 0, true, SlabLds{partw, part, parts, ssw});
 }
 
 }  // namespace
@@ -1283,46 +1119,75 @@ int odin_wgrad_generic(const odin_geom& g, const float* in, const float* dy, flo
   return launch_wgrad(p, rows_out, stream);
 }
 
-// workgroups of job jb that write results (the kernel's three paths), for a launch gx wide
-static int reduce_active_blocks(const odin_reduce_job& jb, int gx) {
+// workgroups of job jb that write results (the body's three paths), for a launch gx wide
+int odin_reduce_active_blocks(const odin_reduce_job& jb, int gx, int* trips_out) {
   const size_t st = jb.stride > 0 ? (size_t)jb.stride : (size_t)jb.n;
   const bool vec = ((jb.n & 3) == 0) && ((st & 3) == 0) && ((((size_t)jb.src | (size_t)jb.dst) & 15) == 0);
   int nb;
   if (vec && (jb.n >> 2) >= 1024) nb = ((jb.n >> 2) + 63) / 64;
   else if (vec) nb = ((jb.n >> 2) + 15) / 16;
   else nb = (jb.n + 31) / 32;
+  if (trips_out) *trips_out = (nb + gx - 1) / gx;
   return nb < gx ? nb : gx;
 }
 
-static int slab_reduce_impl(const odin_reduce_job* jobs, int n_jobs, const float* g_lo, size_t g_n, float* part,
-                            int* n_parts_out, const float* stage_src, float* stage_dst, int stage_n, void* stream) {
+// the plan of one launch's worth of jobs (slab_reduce.h); pnext: partials of the chunks before this one
+static void plan_chunk(const odin_reduce_job* jobs, int nj, uint64_t skip, const float* g_lo, size_t g_n, float* part,
+                       ReduceJobs* rj, int* nj_out, int* gx_out, int* pnext) {
+  memset(rj, 0, sizeof(*rj));
+  int max_n = 0;
+  for (int j = 0; j < nj; ++j)
+    if (jobs[j].n > max_n) max_n = jobs[j].n;
+  int gx = (max_n + 63) / 64;  // vector jobs: 64 floats per block
+  if (gx > 4096) gx = 4096;
+  if (gx < 1) gx = 1;
+  rj->part = part;
+  int k = 0;
+  for (int j = 0; j < nj; ++j) {
+    const odin_reduce_job& jb = jobs[j];
+    const bool in_g = g_lo != nullptr && jb.dst >= g_lo && jb.dst + jb.n <= g_lo + g_n;
+    const int cnt = in_g ? odin_reduce_active_blocks(jb, gx, nullptr) : 0;
+    if (!((skip >> j) & 1)) {
+      rj->j[k] = jb;
+      rj->poff[k] = in_g ? *pnext : -1;
+      rj->pcnt[k] = cnt;
+      ++k;
+    }
+    *pnext += cnt;
+  }
+  *nj_out = k;
+  *gx_out = gx;
+}
+
+int odin_slab_reduce_plan(const odin_reduce_job* jobs, int n_jobs, uint64_t skip, const float* g_lo, size_t g_n,
+                          float* part, ReduceJobs* rj, int* nj_out, int* gx_out, int* n_parts_out) {
+  if (n_jobs < 1 || n_jobs > MAX_JOBS) return odin_fail(-2, "slab_reduce plan: 1 .. 64 jobs");
+  int pnext = 0;
+  plan_chunk(jobs, n_jobs, skip, g_lo, g_n, part, rj, nj_out, gx_out, &pnext);
+  if (n_parts_out) *n_parts_out = pnext;
+  return 0;
+}
+
+static int slab_reduce_impl(const odin_reduce_job* jobs, int n_jobs, uint64_t skip, const float* g_lo, size_t g_n,
+                            float* part, int* n_parts_out, const float* stage_src, float* stage_dst, int stage_n,
+                            void* stream) {
   if (int rc = odin_wgrad_planes_flush(stream)) return rc;  // (deferred weight gradients write the slabs read here)
   if (n_parts_out) *n_parts_out = 0;
   if (n_jobs <= 0) return 0;
   int pnext = 0;
   for (int j0 = 0; j0 < n_jobs; j0 += MAX_JOBS) {
     ReduceJobs rj;
-    memset(&rj, 0, sizeof(rj));
-    int nj = n_jobs - j0 < MAX_JOBS ? n_jobs - j0 : MAX_JOBS;
-    int max_n = 0;
-    for (int j = 0; j < nj; ++j) {
-      rj.j[j] = jobs[j0 + j];
-      if (jobs[j0 + j].n > max_n) max_n = jobs[j0 + j].n;
-    }
-    int gx = (max_n + 63) / 64;  // vector jobs: 64 floats per block
-    if (gx > 4096) gx = 4096;
-    if (gx < 1) gx = 1;
-    rj.part = part;
-    for (int j = 0; j < nj; ++j) {
-      const odin_reduce_job& jb = rj.j[j];
-      const bool in_g = g_lo != nullptr && jb.dst >= g_lo && jb.dst + jb.n <= g_lo + g_n;
-      rj.poff[j] = in_g ? pnext : -1;
-      rj.pcnt[j] = in_g ? reduce_active_blocks(jb, gx) : 0;
-      pnext += rj.pcnt[j];
-    }
+    int nj = n_jobs - j0 < MAX_JOBS ? n_jobs - j0 : MAX_JOBS, nl = 0, gx = 1;
+    plan_chunk(jobs + j0, nj, skip, g_lo, g_n, part, &rj, &nl, &gx, &pnext);   // (skip != 0: one chunk, checked by the caller)
     if (j0 == 0) { rj.stage_src = stage_src; rj.stage_dst = stage_dst; rj.stage_n = stage_n; }
     if (part == nullptr && g_lo != nullptr) continue;  // dry run: only the number of partials
-    dim3 grid(gx, nj, 1), block(256);
+    if (nl == 0) {
+      // every job was reduced elsewhere: workgroup (0, 0) still stages the hyper row (a job of no elements writes nothing)
+      if (stage_dst == nullptr) continue;
+      rj.poff[0] = -1;
+      nl = gx = 1;
+    }
+    dim3 grid(gx, nl, 1), block(256);
     ODIN_LAUNCH(slab_reduce_kernel, grid, block, 0, stream, rj);
     int rc = odin_check_launch("slab_reduce");
     if (rc) return rc;
@@ -1332,7 +1197,7 @@ static int slab_reduce_impl(const odin_reduce_job* jobs, int n_jobs, const float
 }
 
 extern "C" int odin_slab_reduce(const odin_reduce_job* jobs, int n_jobs, void* stream) {
-  return slab_reduce_impl(jobs, n_jobs, nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0, stream);
+  return slab_reduce_impl(jobs, n_jobs, 0, nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0, stream);
 }
 
 // odin_slab_reduce that also leaves the squared norm of the gradient it writes: one partial per active workgroup in
@@ -1344,7 +1209,21 @@ extern "C" int odin_slab_reduce_sumsq(const odin_reduce_job* jobs, int n_jobs, c
                                       int* n_parts_out, const float* stage_src, float* stage_dst, int stage_n,
                                       void* stream) {
   if (g == nullptr || stage_n < 0 || stage_n > 256) return odin_fail(-2, "odin_slab_reduce_sumsq: bad arguments");
-  return slab_reduce_impl(jobs, n_jobs, g, g_n, part, n_parts_out, stage_src, stage_dst, stage_n, stream);
+  return slab_reduce_impl(jobs, n_jobs, 0, g, g_n, part, n_parts_out, stage_src, stage_dst, stage_n, stream);
+}
+
+// the rest of a plan of which odin_neck_bwd_reduce has executed the jobs in `skip_mask` (bit j = job j): the same launch
+// without them -- same grid width, same slices of `part` for the others, *n_parts_out counts the whole list
+extern "C" int odin_slab_reduce_sumsq_masked(const odin_reduce_job* jobs, int n_jobs, uint64_t skip_mask, const float* g,
+                                             size_t g_n, float* part, int* n_parts_out, const float* stage_src,
+                                             float* stage_dst, int stage_n, void* stream) {
+  if (g == nullptr || stage_n < 0 || stage_n > 256) return odin_fail(-2, "odin_slab_reduce_sumsq_masked: bad arguments");
+  if (n_jobs < 1 || n_jobs > MAX_JOBS) return odin_fail(-2, "odin_slab_reduce_sumsq_masked: 1 .. 64 jobs");
+  if (n_jobs < 64 && (skip_mask >> n_jobs) != 0) return odin_fail(-2, "odin_slab_reduce_sumsq_masked: mask beyond the jobs");
+  for (int j = 0; j < n_jobs; ++j)
+    if (((skip_mask >> j) & 1) && !(jobs[j].dst >= g && jobs[j].dst + jobs[j].n <= g + g_n))
+      return odin_fail(-2, "odin_slab_reduce_sumsq_masked: the mask names a job outside the gradient buffer");
+  return slab_reduce_impl(jobs, n_jobs, skip_mask, g, g_n, part, n_parts_out, stage_src, stage_dst, stage_n, stream);
 }
 
 extern "C" int odin_debug_set_wgrad_stamps(void* buf) {

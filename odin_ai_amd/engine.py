@@ -15,7 +15,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-from typing import Callable, Dict, List, NamedTuple, Optional, Sequence, Tuple
+from typing import Any, Callable, Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -508,6 +508,16 @@ class LatentTerm(NamedTuple):
     return None if self.value is None else self.value.data_ptr()
 
 
+def _job_key(jb) -> tuple:
+  """a reduction job as a tuple (the constructor arguments of ReduceJob but the padding)"""
+  return (jb.src, jb.dst, jb.n, jb.rows, jb.stride)
+
+
+def _job_sig(t: tuple) -> tuple:
+  """what the plan of a slab reduction reads of a job it does not execute: dst, n, stride, the alignment of src"""
+  return (t[1], t[2], t[4], (t[0] or 0) & 15)
+
+
 class VAEEngine:
   """encoder -> q(z|x) -> decoder -> ELBO -> backward -> Adam for a FIXED batch size.
 
@@ -526,7 +536,8 @@ class VAEEngine:
                act_words: bool = True, hyper_ring: bool = True, hyper_ring_rows: int = 128, fuse_norm: bool = True,
                overlap_wgrad: Optional[str] = None, early_reduce: bool = False, defer_wgrad: bool = False,
                fuse_first_wgrad: bool = True, side_streams: int = 2, small_wgrad_gf: float = 0.8, dp_buckets: Optional[int] = None,
-               neck: bool = True, neck_bwd: Optional[bool] = None, static_top_word: bool = True,
+               neck: bool = True, neck_bwd: Optional[bool] = None, neck_reduce: bool = True,
+               static_top_word: bool = True,
                latent_reg: Optional[str] = None, reg_coef: float = 1.0, mmd_kernel: str = 'gaussian',
                mmd_prior_samples: int = 100, dip_lambda: Tuple[float, float] = (1.0, 2.0), prior_seed: int = 0,
                vamprior_components: Optional[int] = None, pseudoinputs_mean: float = -0.05,
@@ -556,6 +567,12 @@ class VAEEngine:
                        Conv2DTranspose as ONE launch per direction where the shapes allow (neck.hip); False: round 5's
                        four launches per direction
       neck_bwd         the neck's backward launch (None: where it was measured faster)
+      neck_reduce      the decoder's slab jobs (complete before the neck's backward launch) reduced by extra workgroups
+                       of that launch, on the CUs it leaves idle; the step's last reduction skips them (DESIGN 3.9b;
+                       odin_neck_bwd_reduce / odin_slab_reduce_sumsq_masked).  Only where that launch is in use, the
+                       norm rides in the reduction, the engine is not data-parallel, and overlap_wgrad, early_reduce and
+                       debug_check_ranges are off; the first step of a job list runs the two plain launches and records
+                       the list, which is the plan of every later step.  Bit-identical; False: the two plain launches
       chain_fwd        the Conv2DTranspose below the fused Bernoulli tail inside the tail's launch, a workgroup running both
                        for its own images (odin_decoder_tail_chain) -- only where the library takes the
                        shapes AND the chain's partition is the tail's own, so that the step's bits do not change; never in
@@ -867,6 +884,10 @@ class VAEEngine:
     assert overlap_wgrad in (None, 'small'), overlap_wgrad
     self.overlap_wgrad = overlap_wgrad
     self.early_reduce = bool(early_reduce)
+    self.neck_reduce = bool(neck_reduce)
+    self._nr_plans: Dict[tuple, Any] = {}   # early jobs -> the jobs that follow them in such a step | False (_neck_bwd)
+    self._nr_state = None
+    self._nr_enough: set = set()
     # the five plane weight gradients of a step as ONE multi-layer launch at the end of the backward pass
     # (odin_wgrad_planes_defer_begin / _end): OFF -- same-box A/B: dSprites 0.491 ms with it, 0.484 without
     # (r05_ab_same_call.txt).  Four launch floors are saved, but issued right behind the data gradient that produced its
@@ -1661,7 +1682,36 @@ class VAEEngine:
                           self.enc.gouts[ne - 3].data_ptr())
     A.dh4_amax, A.dy3_amax, A.dx_amax = self.enc.set_top_word(True), self.enc.word(ne - 2), self.enc.word(ne - 3)
     A.slab1, A.slab0, A.slabl = self.nk_slab1.data_ptr(), self.nk_slab0.data_ptr(), self.nk_slabl.data_ptr()
-    lib.odin_neck_bwd(C.byref(A), st)
+    self._nr_state = None
+    if self._neck_reduce_now(jobs):
+      # `jobs` holds the decoder's jobs (_backward_dec: the layers above the neck and the tail's two), whose slabs are
+      # complete: extra workgroups of this launch reduce them.  The launch needs the plan of the step's WHOLE job list,
+      # which is only known at the end of the pass: the first step with these early jobs runs the plain launches and
+      # _reduce_slabs records the jobs that follow them; later steps are checked against that record there -- in what a
+      # plan reads of a late job (_job_sig: not its rows, not where its slab lies: the label head's job has rows on a
+      # labelled step only).  A record of False: the launch would leave too few CUs to the reducers (odin_neck_reduce_workgroups).
+      key = tuple(_job_key(jb) for jb in jobs)
+      late = self._nr_plans.get(key)
+      if late is None:
+        self._nr_state = ('learn', key)
+      elif late is not False:
+        plan = key + late
+        arr = (ReduceJob * len(plan))(*(ReduceJob(*t, 0) for t in plan))
+        mask = (1 << len(key)) - 1
+        if key not in self._nr_enough:
+          # (asked once per record; 0: the neck's own workgroups leave the reducers too few CUs -- large batches)
+          self._nr_enough.add(key)
+          if lib.odin_neck_reduce_workgroups(C.byref(A), arr, len(plan), mask, self.grads.data_ptr(),
+                                             self.grads.numel()) <= 0:
+            late = self._nr_plans[key] = False
+        if late is not False:
+          # self.ws (the norm partials) is written by this launch and by the step's last reduction, each its own
+          # slices, and read by the Adam launch only: nothing else in this file may use it between the three
+          lib.odin_neck_bwd_reduce(C.byref(A), arr, len(plan), mask, self.grads.data_ptr(), self.grads.numel(),
+                                   self.ws.data_ptr(), -1, st)
+          self._nr_state = ('used', key, late, mask)
+    if self._nr_state is None or self._nr_state[0] != 'used':
+      lib.odin_neck_bwd(C.byref(A), st)
     for slab, off in ((self.nk_slab1, t1.w_off), (self.nk_slab0, d0.w_off), (self.nk_slabl, self.lat_w_off)):
       jobs.append(self._slab_job(slab, off, self.nk_rows))
     # conv3's weight gradient (a reduction over all B * 16 pixels) and the projection's (over the batch)
@@ -1679,6 +1729,12 @@ class VAEEngine:
     finally:
       lib.odin_wgrad_pair_end()   # (a launch that failed inside the pair must not leave it open for the next step)
     jobs.append(self._slab_job(slab, d4.w_off, wrows.value))
+
+  def _neck_reduce_now(self, jobs) -> bool:
+    """may this pass's neck backward launch reduce `jobs` (VAEEngine(neck_reduce=))?"""
+    return bool(self.neck_reduce and jobs and len(jobs) <= 64 and getattr(self, '_fuse_norm_now', False) and
+                not self.is_dp and not self.overlap_wgrad and not self.early_reduce and not self.defer_wgrad and
+                not self.debug_check_ranges)
 
   def _bwd_neck(self) -> bool:
     if not (self.neck and self._used_neck) or (self.is_dp and self.dp_buckets >= 2):
@@ -2204,6 +2260,7 @@ class VAEEngine:
     data-parallel step all-reduces the decoder's gradients while 'enc' runs."""
     lib = self.lib
     st = self.stream() if st is None else st
+    self._nr_state = None   # (a pass that failed behind the neck's launch must not leave its note to this one)
     if phase == 'dec':
       jobs, _, _ = self._backward_dec(st, None)
       arr = (ReduceJob * len(jobs))(*jobs)
@@ -2362,6 +2419,20 @@ class VAEEngine:
                                  first=self._dec_first() - 1 if self._bwd_neck() else 0)
       self.enc.check_range_words()
     self._norm_parts = 0
+    nr, self._nr_state = self._nr_state, None
+    if nr is not None and nr[0] == 'used':
+      # the neck's backward launch has reduced the jobs in nr[2] on the plan nr[1]: the pass must have built that list
+      ne = len(nr[1])
+      if (tuple(_job_key(jb) for jb in jobs[:ne]) != nr[1] or
+          [_job_sig(_job_key(jb)) for jb in jobs[ne:]] != [_job_sig(t) for t in nr[2]]):
+        raise RuntimeError('neck_reduce: the job list of this step differs from the plan its early jobs were reduced on')
+      nparts = C.c_int(0)
+      lib.odin_slab_reduce_sumsq_masked(arr, len(jobs), nr[3], self.grads.data_ptr(), self.grads.numel(),
+                                        self.ws.data_ptr(), C.byref(nparts), self.hyper.data_ptr(),
+                                        self.hyper_staged.data_ptr(), N_HYPER + 4, st)
+      assert 0 < nparts.value <= self.ws.numel(), (nparts.value, self.ws.numel())
+      self._norm_parts = nparts.value
+      return
     if getattr(self, '_fuse_norm_now', False) and not early:
       # the gradient norm's stage-1 launch rides in the reduction (include/odin_hip.h: odin_slab_reduce_sumsq) -- its
       # jobs tile the flat gradient buffer exactly once (checked on the first call) -- and the launch stages this step's
@@ -2378,12 +2449,21 @@ class VAEEngine:
           lib.odin_slab_reduce_sumsq(arr, len(jobs), self.grads.data_ptr(), self.grads.numel(), None, C.byref(nparts),
                                      None, None, 0, st)
           ok = 0 < nparts.value <= 2048
+        elif not (any(self.enc.wdirect) or any(self.dec.wdirect)):
+          # (without direct-write layers every gradient slice arrives through exactly one job: anything else is a bug in
+          # a job list, and the fallback below would train on a wrong norm -- or, with neck_reduce, a slice reduced twice)
+          raise RuntimeError('the reduction jobs of this step do not tile the flat gradient buffer exactly once')
         self._jobs_cover_ok[sig] = ok
       if not ok:
         # (a parameter whose gradient does not arrive through a slab job, or too many partials: the norm keeps its own
         # stage-1 launch -- odin_sumsq_adam_ring in adam())
         lib.odin_slab_reduce(arr, len(jobs), st)
         return
+      if nr is not None and nr[0] == 'learn' and len(jobs) <= 64:
+        # the early jobs lead the list (the mask of _neck_bwd names the first len(key) jobs)
+        ne = len(nr[1])
+        assert tuple(_job_key(jb) for jb in jobs[:ne]) == nr[1], 'neck_reduce: the early jobs do not lead the job list'
+        self._nr_plans[nr[1]] = tuple(_job_key(jb) for jb in jobs[ne:])
       lib.odin_slab_reduce_sumsq(arr, len(jobs), self.grads.data_ptr(), self.grads.numel(), self.ws.data_ptr(),
                                  C.byref(nparts), self.hyper.data_ptr(), self.hyper_staged.data_ptr(), N_HYPER + 4, st)
       assert 0 < nparts.value <= self.ws.numel(), (nparts.value, self.ws.numel())
