@@ -592,7 +592,10 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ theta,
   if (gnorm2 != nullptr || parts != nullptr) {
     float n2 = parts != nullptr ? n2_sh : gnorm2[0];
     // NaN / Inf gradients: skip the update and raise the flag -- unless the caller passed no flag
-    // (nan_gradients_policy='ignore', base_networks.py:519-547: the update is applied whatever the gradients hold)
+    // (nan_gradients_policy='ignore', base_networks.py:519-547: the update is applied whatever the gradients hold).
+    // A skipped step is still a step: workgroup 0 has advanced `cur` to the next ring row above, the stage-1 launch
+    // has staged this step's scalars and the ELBO outputs are finalised -- the host's ring bookkeeping counts every
+    // step, skipped or not (pinned by tests/test_optimizer_step.py::test_non_finite_gradient)
     if ((!(n2 == n2) || n2 > 3.0e38f) && flag != nullptr) {
       if (blockIdx.x == 0 && threadIdx.x == 0) flag[0] = 1;
       return;
